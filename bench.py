@@ -12,6 +12,12 @@ timed region.  Multi-GPU: one process per GPU (torchrun), chains sharded (global
 chain index -> PCG64 seed 42+g and proposal-stream row), no per-step collective;
 the final density histogram and well-occupancy counters are all-reduced (RCCL).
 
+A plain run sets up, warms up, times the steps, writes the last step's outputs when
+--dump-outputs is given and prints the result line.  Every secondary measurement and
+check (acceptance-rate match against the oracle, other precisions, single-pass log q,
+supplied proposals, configs 2 and 5, the Algorithm-1 regime, the CPU baselines) runs
+only with --full.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -771,6 +777,47 @@ def acceptance_match(bmc, stepper, n_chains=2048, steps=10, f64_steps=4):
             "oracle_s": time.perf_counter() - t0}
 
 
+DUMP_ROWS = 8192  # chains whose (C, 2N) rows are written by --dump-outputs
+# a proposal with overlapping particles has an infinite energy (and is rejected): these
+# arrays are written finite, beside a <name>_nonfinite array of 0 finite, 1 +inf, 2 -inf, 3 NaN
+DUMP_NONFINITE_CODED = ("log_q", "E_new", "W_new")
+
+
+def dump_outputs(path, bmc, stepper, reduction, rank, world):
+    """--dump-outputs: what the timed path computed in its last step, as <name>.npy files
+    (float32 / float64; <name>.rank<r>.npy when sharded) under `path`.  The per-chain
+    values of every chain: the proposals' log q, energy and well term, the accept
+    decisions, and the running energy, NLL and counters after the step.  The (C, 2N)
+    arrays (proposals in box and centred coordinates, the chains' states) are written
+    for a fixed sample of DUMP_ROWS chains (seeded, the same for every run of the same
+    --chains; their indices in `rows`), about 23 MB in all at the default size.  Also
+    the end reduction of the timed region: density histogram, well totals and the
+    gathered per-chain counters.  Every file holds finite numbers only: where a value is
+    infinite or NaN it is written as 0 and its kind in <name>_nonfinite.npy
+    (DUMP_NONFINITE_CODED; any other array gets such a file only if it needs one)."""
+    C = bmc.C
+    rows = np.arange(C) if C <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(C, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(bmc.device)
+    hist, wells, table = reduction
+    out = {"rows": rows.astype(np.float64),
+           "proposal": stepper.config[idx], "proposal_centered": stepper.centered[idx],
+           "log_q": stepper.log_q, "E_new": stepper.E_new, "W_new": stepper.W_new,
+           "accept": bmc.accept.float(), "state": bmc.state[idx].double().reshape(len(rows), -1),
+           "E_old": bmc.E_old, "W_old": bmc.W_old, "nll_old": bmc.nll_old,
+           "accepted": bmc.accepted.double(), "attempts": bmc.attempts.double(),
+           "hist": hist.double(), "wells": wells.double(), "chain_counters": table.double()}
+    os.makedirs(path, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        cls = np.select([np.isposinf(a), np.isneginf(a), np.isnan(a)], [1.0, 2.0, 3.0], 0.0).astype(np.float32)
+        if name in DUMP_NONFINITE_CODED or cls.any():
+            a = np.where(cls == 0, a, 0).astype(a.dtype)
+            np.save(os.path.join(path, f"{name}_nonfinite{sfx}.npy"), cls)
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), a)
+
+
 def _launch_ranks(n):
     """python -m torch.distributed.run --nproc-per-node n bench.py <same args>, on
     127.0.0.1 and a free port; returns its exit code (rank 0 prints the JSON line)."""
@@ -792,6 +839,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--chains", type=int, default=65536, help="chains per GPU")
     ap.add_argument("--particles", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also run every secondary measurement and check (acceptance-rate "
+                         "match, other precisions, single-pass log q, supplied proposals, configs 2 and 5, the "
+                         "Algorithm-1 regime, CPU baselines); the --no-* switches below take single ones out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")
@@ -813,6 +866,8 @@ def main():
                     help="write each rank's final per-chain state to DUMP.rank<r>.npz (rehearsals: a sharded "
                          "run must hold the chains a 1-rank run over the same global chains holds)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `bench.py --gpus N` outside a launcher: start the N rank processes here, as fresh
@@ -871,6 +926,8 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     bmc.check_errors()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bmc, stepper, (hist, wells, table), rank, world)
     if args.dump:
         np.savez(f"{args.dump}.rank{rank}.npz", chain_offset=c0, state=bmc.state.cpu().numpy(),
                  state_is_f32=bmc.state_is_f32.cpu().numpy(), E_old=bmc.E_old.cpu().numpy(),
@@ -961,24 +1018,25 @@ def main():
             out[name] = {"error": f"{type(e).__name__}: {e}"}
             print(f"bench.py: {name} failed: {e!r}", file=sys.stderr, flush=True)
 
-    out["parity_checked"] = None  # the acceptance-rate match runs on rank 0 at N=1 only
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    out["parity_checked"] = None  # the acceptance-rate match runs on rank 0 at N=1 with --full only
+    full = args.full and world == 1  # the secondary legs: one GPU, --full
+    if full and rank == 0 and not args.no_cpu_baseline:
         leg("acceptance_match", acceptance_match, bmc, stepper)
         am = out["acceptance_match"]
         # the metric's qualifier: true only when the replay ran and matched every decision
         # made on identical inputs (an errored check is false, never a clean run)
         out["parity_checked"] = "error" not in am and am["mismatched_on_identical_inputs"] == 0
-    if world == 1 and not args.no_alt_precision and args.precision == "f32":
+    if full and not args.no_alt_precision and args.precision == "f32":
         leg("alt_precision", alt_precisions, bmc, stepper)
-    if world == 1 and not args.no_single_pass and args.precision == "f32":
+    if full and not args.no_single_pass and args.precision == "f32":
         leg("single_pass", single_pass, bmc, stepper)
-    if world == 1 and not args.no_given_proposal:
+    if full and not args.no_given_proposal:
         leg("given_proposal", given_proposal, bmc, stepper)
-    if world == 1 and not args.no_config2:
+    if full and not args.no_config2:
         leg("config2", config2)
-    if world == 1 and not args.no_config5:
+    if full and not args.no_config5:
         leg("config5", config5)
-    if world == 1 and not args.no_algorithm1_regime:
+    if full and not args.no_algorithm1_regime:
         leg("algorithm1_regime", algorithm1_regime)
         if not args.no_cpu_baseline and "error" not in out["algorithm1_regime"]:
             reg = out["algorithm1_regime"]
@@ -987,7 +1045,7 @@ def main():
                 reg["vs_cpu_baseline"] = reg["value"] / reg["cpu_baseline"]["value"]
             except Exception as e:  # noqa: BLE001
                 reg["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if full and rank == 0 and not args.no_cpu_baseline:
         leg("cpu_baseline", cpu_baseline, N, args.cpu_budget)
         # vs_baseline stays null: BASELINE.md has no published number for this metric
         if "value" in out["cpu_baseline"]:
