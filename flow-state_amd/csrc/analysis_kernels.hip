@@ -231,9 +231,140 @@ __global__ void rdf_mean_kernel(const int32_t *__restrict__ counts, int64_t M, i
     g[k] = s / (double)M;
 }
 
+// One analysis batch of the Algorithm-2 checkpoint cycle (main_algorithm_2.py:493-525)
+// in one launch, float32 as the reference's numpy arrays are:
+//   a_  = a + HALF_BOX          -> out (the rows of samples.npy)
+//   c   = a_ - HALF_BOX         (HALF_BOX rounded to float32 both times: weak scalar)
+//   np.histogram2d(c)           -> hist += (hist2d_lds_kernel's rule on (double)c)
+//   pair-distance counts of c   -> counts (pair_hist_kernel<float>'s arithmetic)
+// One wave per configuration, four per workgroup, the workgroup striding over the
+// batch; the 2-D histogram is private to the workgroup in LDS (uint32: a workgroup bins
+// far fewer than 2^32 particles) and its non-empty bins are flushed once at the end.
+// All LDS is dynamic (16-byte carve offsets): at nb = 120 it passes 64 KiB.
+constexpr int kSaRBins = 128, kSaN = 256;  // pair_hist_kernel's bounds (nb <= 120 as hist2d_lds_kernel: capi.cpp)
+
+struct SaLds {
+    int e2, er, h2, hp, sx, sy, bytes;
+};
+__host__ __device__ inline SaLds sa_lds(int nb, int nr) {
+    auto up = [](int v) { return (v + 15) & ~15; };
+    SaLds L;
+    int o = 0;
+    L.e2 = o, o = up(o + (nb + 1) * 8);
+    L.er = o, o = up(o + (nr + 1) * 8);
+    L.h2 = o, o = up(o + nb * nb * 4);
+    L.hp = o, o += 4 * kSaRBins * 4;
+    L.sx = o, o += 4 * kSaN * 4;
+    L.sy = o, o += 4 * kSaN * 4;
+    L.bytes = o;
+    return L;
+}
+
+// k with e[k] <= v < e[k+1], for sorted edges e[0..n] and e[0] <= v < e[n]: the bin an
+// evenly spaced grid would give (inv_w = n / (e[n] - e[0])), then steps along the edges
+// until the inequalities hold.  The result is searchsorted's for any sorted edges; with
+// linspace / arange edges it takes two or three LDS reads instead of a binary search's
+// log2(n) dependent ones.
+__device__ inline int bin_near(const double *e, int n, double inv_w, double v) {
+    int k = (int)((v - e[0]) * inv_w);
+    k = k < 0 ? 0 : (k > n - 1 ? n - 1 : k);
+    while (k > 0 && e[k] > v) --k;
+    while (k < n - 1 && e[k + 1] <= v) ++k;
+    return k;
+}
+
+__global__ void __launch_bounds__(256) sample_analysis_kernel(const float *__restrict__ z, int64_t M, int N,
+                                                              double half_box, const double *__restrict__ edges2,
+                                                              int nb, const double *__restrict__ edges_r, int nr,
+                                                              float *__restrict__ out,
+                                                              unsigned long long *__restrict__ hist,
+                                                              int32_t *__restrict__ counts) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const SaLds L = sa_lds(nb, nr);
+    double *e2 = (double *)(smem + L.e2), *er = (double *)(smem + L.er);
+    unsigned int *h2 = (unsigned int *)(smem + L.h2);
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int32_t *hp = (int32_t *)(smem + L.hp) + wid * kSaRBins;
+    float *sx = (float *)(smem + L.sx) + wid * kSaN, *sy = (float *)(smem + L.sy) + wid * kSaN;
+    for (int i = threadIdx.x; i < nb * nb; i += blockDim.x) h2[i] = 0u;
+    for (int i = threadIdx.x; i <= nb; i += blockDim.x) e2[i] = edges2[i];
+    for (int i = threadIdx.x; i <= nr; i += blockDim.x) er[i] = edges_r[i];
+    __syncthreads();
+    const double inv2 = (double)nb / (e2[nb] - e2[0]);
+    auto bin_of = [&](double v) {  // np.searchsorted(edges, v, 'right') - 1, last edge inclusive
+        if (!(v >= e2[0])) return -1;
+        if (v >= e2[nb]) return v == e2[nb] ? nb - 1 : nb;
+        return bin_near(e2, nb, inv2, v);
+    };
+    const float hb = (float)half_box, tb = (float)(2.0 * half_box);
+    const double e0 = er[0], elast = er[nr];
+    const double invr = (double)nr / (elast - e0);
+    for (int64_t m0 = (int64_t)blockIdx.x * 4; m0 < M; m0 += (int64_t)gridDim.x * 4) {
+        const int64_t m = m0 + wid;
+        if (m >= M) continue;  // wave-uniform
+        for (int k = lane; k < nr; k += 64) hp[k] = 0;
+        const float *q = z + m * (int64_t)N * 2;
+        float *o = out + m * (int64_t)N * 2;
+        for (int i = lane; i < N; i += 64) {
+            const float ax = q[2 * i] + hb, ay = q[2 * i + 1] + hb;
+            o[2 * i] = ax;
+            o[2 * i + 1] = ay;
+            const float cx = ax - hb, cy = ay - hb;
+            sx[i] = cx;
+            sy[i] = cy;
+            const int bx = bin_of((double)cx), by = bin_of((double)cy);
+            if (bx >= 0 && bx < nb && by >= 0 && by < nb) atomicAdd(&h2[bx * nb + by], 1u);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int i = lane; i < N; i += 64) {
+            const float xi = sx[i], yi = sy[i];
+            for (int j = 0; j < N; ++j) {
+                float dx = xi - sx[j], dy = yi - sy[j];
+                dx = dx - tb * (float)rint(dx / tb);
+                dy = dy - tb * (float)rint(dy / tb);
+                const float s0 = dx * dx, s1 = dy * dy;
+                const float s = s0 + s1;
+                const double d = (double)(float)sqrt(s);
+                if (d == 0.0 || d < e0 || d > elast) continue;
+                // edges[lo] <= d < edges[lo+1], last bin right-inclusive
+                const int lo = d >= elast ? nr - 1 : bin_near(er, nr, invr, d);
+                atomicAdd(&hp[lo], 1);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int k = lane; k < nr; k += 64) counts[m * nr + k] = hp[k];
+        // the next configuration of this wave reuses hp / sx / sy
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nb * nb; i += blockDim.x)
+        if (h2[i]) atomicAdd(&hist[i], (unsigned long long)h2[i]);
+}
+
 }  // namespace fs
 
 using namespace fs;
+
+hipError_t fs_sample_analysis_impl(const float *z, int64_t M, int N, double half_box, const double *edges2, int nb,
+                                   const double *edges_r, int nr, float *out, int64_t *hist, int32_t *counts,
+                                   hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    static std::atomic<unsigned long long> lds_done{0};
+    if (hipError_t e = fs_set_max_lds_once((const void *)sample_analysis_kernel, lds_done); e != hipSuccess) return e;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int64_t want = (M + 3) / 4, cap = 2 * (int64_t)cus;
+    const unsigned blocks = (unsigned)(want < cap ? want : cap);
+    hipLaunchKernelGGL(sample_analysis_kernel, dim3(blocks), dim3(256), (size_t)sa_lds(nb, nr).bytes, st, z, M, N,
+                       half_box, edges2, nb, edges_r, nr, out, (unsigned long long *)hist, counts);
+    return hipGetLastError();
+}
 
 hipError_t fs_classify_wells_impl(const void *pos, int f32, int64_t M, int N, double half_box, double r0,
                                   uint8_t *cls, uint8_t *state, double *avg_x, hipStream_t st) {

@@ -550,6 +550,20 @@ int fs_rdf_mean(const int32_t *counts, int64_t M, int32_t nbins, const double *d
     return hip_rc(fs_rdf_mean_impl(counts, M, nbins, denom, g_r, (hipStream_t)stream), "fs_rdf_mean");
 }
 
+int fs_sample_analysis(const float *z, int64_t M, int32_t N, double half_box, const double *hist_edges, int32_t nbins,
+                       const double *r_edges, int32_t r_nbins, float *samples_out, int64_t *hist, int32_t *counts,
+                       void *stream) {
+    REQUIRE(hist_edges && r_edges && M >= 0 && N >= 1 && half_box > 0.0 &&
+                (M == 0 || (z && samples_out && hist && counts)),
+            "fs_sample_analysis: invalid arguments");
+    REQUIRE(N <= 256 && nbins >= 1 && nbins <= 120 && r_nbins >= 1 && r_nbins <= 128,
+            "fs_sample_analysis: N <= 256, 1 <= nbins <= 120 and 1 <= r_nbins <= 128 (got %d, %d, %d)", N, nbins,
+            r_nbins);
+    return hip_rc(fs_sample_analysis_impl(z, M, N, half_box, hist_edges, nbins, r_edges, r_nbins, samples_out, hist,
+                                          counts, (hipStream_t)stream),
+                  "fs_sample_analysis");
+}
+
 }  // extern "C"
 
 int fs_linear_f32(int64_t M, int64_t N, int64_t K, const float *A, int64_t sam, int64_t sak, const float *B,

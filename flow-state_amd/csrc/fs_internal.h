@@ -53,6 +53,9 @@ hipError_t fs_classify_wells_impl(const void *pos, int f32, int64_t M, int N, do
 hipError_t fs_pair_hist_impl(const void *pos, int f32, int64_t M, int N, double bound, const double *edges, int nb,
                              int32_t *counts, hipStream_t st);
 hipError_t fs_rdf_mean_impl(const int32_t *counts, int64_t M, int nb, const double *denom, double *g, hipStream_t st);
+hipError_t fs_sample_analysis_impl(const float *z, int64_t M, int N, double half_box, const double *edges2, int nb,
+                                   const double *edges_r, int nr, float *out, int64_t *hist, int32_t *counts,
+                                   hipStream_t st);
 hipError_t fs_rqs_forward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
                                const float *ud, float B, float *out, float *lad, int32_t *nan_flag, hipStream_t st);
 hipError_t fs_rqs_backward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,

@@ -171,6 +171,8 @@ _SIGS = {
     "fs_pair_hist": (ctypes.c_int, [_P, ctypes.c_int, _I64, ctypes.c_int32, ctypes.c_double, _P, ctypes.c_int32,
                                     _P, _P]),
     "fs_rdf_mean": (ctypes.c_int, [_P, _I64, ctypes.c_int32, _P, _P, _P]),
+    "fs_sample_analysis": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_double, _P, ctypes.c_int32, _P,
+                                          ctypes.c_int32, _P, _P, _P, _P]),
     "fs_hist2d": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_double, _P, ctypes.c_int32, _P, _P]),
     "fs_well_stats": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P]),
 }

@@ -12,6 +12,11 @@ A cycle is
   refeeding    model.eval(); one flow proposal per run (model.sample(NUM_MC_RUNS) +
                HALF_BOX) offered through nf_big_move (:476-540).
 
+With checkpoint_interval set, run() also does the reference's checkpoint-cycle work between
+training and refeeding (:458-526: loss file, model checkpoint, the analysis batch of
+NUM_SAMPLES_FOR_ANALYSIS flow samples with samples.npy, the heat-map and g(r) files) and
+writes p_acc_history_data.json after the loop (:588-599); plots are not drawn.
+
 Device mapping: production and refeeding are one batched call each over all runs (the
 refeed is the fused fs_nf_mh_step: in-kernel base draws -> sampling pass -> density
 pass -> energies -> accept); training runs through PyTorch-ROCm autograd with the
@@ -52,13 +57,32 @@ def _first(batch):
     return batch
 
 
+def is_checkpoint_cycle(cycle, interval, cycles):
+    """main_algorithm_2.py:459/485/566 for the 0-based `cycle` of `cycles`: the loss file,
+    the analysis batch and its files."""
+    return (cycle + 1) % interval == 0 or cycle == cycles - 1
+
+
+def saves_model(cycle, interval, cycles):
+    """main_algorithm_2.py:468: `(cycle + 1) % CHECKPOINT_INTERVAL*2 == 0` parses as
+    ((cycle + 1) % CHECKPOINT_INTERVAL) * 2 == 0, so the model is saved on the same
+    cycles as the analysis runs, not on every second checkpoint."""
+    return ((cycle + 1) % interval) * 2 == 0 or cycle == cycles - 1
+
+
 class Algorithm2:
     def __init__(self, bmc, model, batch_size=256, lr=0.000543510751759681, weight_decay=9.5857178422352e-05,
                  alpha=1.0, sampling_frequency=10, update_num_samples=1000, num_mc_runs=None, cumulative=False,
-                 graphed=True, group=None):
+                 graphed=True, group=None, checkpoint_interval=None, num_samples_for_analysis=50000, out_dir=None,
+                 initial_p_acc=0.0, initial_training_num_samples=None, cmap_name=None):
         """bmc: this rank's BatchedMonteCarlo (its runs); model: the flow (the same
         initial weights on every rank); num_mc_runs: NUM_MC_RUNS over all ranks
-        (default: bmc.C x world size).  Defaults are main_algorithm_2.py:32-64."""
+        (default: bmc.C x world size).  Defaults are main_algorithm_2.py:32-64.
+        checkpoint_interval (CHECKPOINT_INTERVAL; None: no checkpoint work, run() as
+        without it) with out_dir turns on run()'s checkpoint-cycle outputs:
+        num_samples_for_analysis flow samples per analysis batch, initial_p_acc and
+        initial_training_num_samples (INITIAL_TRAINING_NUM_SAMPLES, required) open
+        p_acc_history_data.json, cmap_name is stored in the heat-map JSON."""
         self.bmc, self.model = bmc, model
         self.batch_size, self.lr, self.wd, self.alpha = int(batch_size), float(lr), float(weight_decay), float(alpha)
         self.sf = int(sampling_frequency)
@@ -75,6 +99,18 @@ class Algorithm2:
         self.graphed = bool(graphed) and next(model.parameters()).is_cuda
         self._step = None
         self._mods = None  # (model, its modules) for the mode switches (_set_training)
+        self.update_num_samples = int(update_num_samples)
+        self.checkpoint_interval = None if checkpoint_interval is None else int(checkpoint_interval)
+        self.num_samples_for_analysis = int(num_samples_for_analysis)
+        self.out_dir = out_dir
+        self.initial_p_acc = initial_p_acc
+        self.initial_training_num_samples = initial_training_num_samples
+        self.cmap_name = cmap_name
+        self.last_analysis = None  # the latest checkpoint cycle's analysis.sample_analysis result
+        self._analysis_gen = None
+        if self.checkpoint_interval is not None:
+            if self.checkpoint_interval < 1 or out_dir is None or initial_training_num_samples is None:
+                raise ValueError("checkpoint_interval >= 1 needs out_dir and initial_training_num_samples")
 
     # ------------------------------------------------------------------
     def production(self):
@@ -226,10 +262,71 @@ class Algorithm2:
                     if more:
                         spec.begin(n, sf)
                     loss = self.train()
+                    if self.checkpoint_interval is not None:
+                        self._checkpoint(c, cycles)
                     acc, p = self.refeed()
                     out.append((snap, loss, acc, p))
                     ahead = spec.finish(n, sf) if more else None
             finally:
                 if spec is not None:
                     spec.close()
+        if self.checkpoint_interval is not None and self._rank() == 0:
+            from . import io
+
+            io.write_p_acc_history(self.out_dir, [self.initial_p_acc] + self.p_acc_history,
+                                   self.initial_training_num_samples, self.update_num_samples)
         return out
+
+    # ------------------------------------------------------------------
+    def _rank(self):
+        import torch.distributed as dist
+
+        return dist.get_rank(self.group) if self.world > 1 else 0
+
+    def _checkpoint(self, c, cycles):
+        """main_algorithm_2.py:458-526 between training and the refeed of 0-based cycle c:
+        the loss file, the model checkpoint, then (model.eval()) the analysis batch with
+        samples.npy, the heat-map and the g(r) files.  Rank 0 only (the reference analyses
+        on one device); main stream, so the speculative production beside it is untouched.
+        The analysis draws come from a device generator of their own: neither the host
+        generator (training batch order) nor the device's default one (reverse_kld's base
+        draws) moves, so the chains are those of a run without checkpoints."""
+        import os
+
+        from . import analysis, io
+
+        k = self.checkpoint_interval
+        if self._rank() != 0 or not (is_checkpoint_cycle(c, k, cycles) or saves_model(c, k, cycles)):
+            return
+        os.makedirs(self.out_dir, exist_ok=True)
+        if is_checkpoint_cycle(c, k, cycles):
+            io.write_loss_history(self.out_dir, self.loss_history)
+        if saves_model(c, k, cycles):
+            io.save_model_checkpoint(self.out_dir, c + 1, self.model)
+        if not is_checkpoint_cycle(c, k, cycles):
+            return
+        self._set_training(False)  # model.eval() (:476)
+        dev = next(self.model.parameters()).device
+        if self._analysis_gen is None or self._analysis_gen.device != dev:
+            self._analysis_gen = torch.Generator(device=dev)
+            self._analysis_gen.manual_seed((torch.initial_seed() + 1) % 2 ** 63)  # not the default stream's
+        res = analysis.sample_analysis(self.model, self.num_samples_for_analysis, self.bmc.phys.half_width,
+                                       generator=self._analysis_gen)
+        io.save_samples(self.out_dir, res["samples"])
+        io.write_frequency_heatmap(self.out_dir, c + 1, res["hist"], res["x_edges"], res["y_edges"], self.cmap_name)
+        io.write_pair_correlation(self.out_dir, c + 1, res["r_vals"], res["g_r"])
+        self.last_analysis = res
+
+    def well_statistics(self, snapshots, start_idx, r0=1.2):
+        """main_algorithm_2.py:620-668 over this rank's runs: every run's testing
+        configurations (the production snapshots of the cycles, in order) from start_idx on
+        -> (algorithm1.well_statistics(...), algorithm1.free_energy_curve(deltaF)).  A run
+        counts as float32 only if every snapshot of it was (TestingResult.testing_is_f32:
+        np.array over the whole list before the slice)."""
+        snaps = list(snapshots)
+        xy = torch.cat([s.xy for s in snaps], 1)[:, start_idx:]
+        f32 = torch.ones_like(snaps[0].is_f32)
+        for s in snaps:
+            f32 &= s.is_f32
+        stats = A1.well_statistics(xy.contiguous(), f32, self.bmc.phys.half_width, r0)
+        return stats, A1.free_energy_curve(stats[3])

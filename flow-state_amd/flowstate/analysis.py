@@ -6,6 +6,11 @@ signatures, computed by the HIP kernels of csrc/analysis_kernels.hip:
   calculate_pair_correlation(final_samples, n_particles, bound, dr)   utils.py:530-574
   generate_samples(model, n_particles, n_dimension, ...)            utils.py:422-450
 
+and the analysis batch of the Algorithm-2 driver's checkpoint cycles
+(main_algorithm_2.py:485-525; fs_sample_analysis, one launch per 1000-row batch):
+
+  sample_analysis(model, n_samples, half_box, batch=1000, bins=100, dr=None)
+
 Inputs are numpy arrays or device tensors; float32 and float64 inputs keep
 numpy's dtype semantics (the kernels reproduce numpy 2's weak-Python-float
 promotion).  The host side only does the per-configuration bookkeeping of the
@@ -92,20 +97,96 @@ def calculate_pair_correlation(final_samples, n_particles, bound, dr=None):
 
     if dr is None:
         dr = bound / 50
-    edges = np.arange(0, bound + dr, dr)
+    edges, denom, r_vals = _rdf_bins(n_particles, bound, dr)
     counts = pair_histograms(final_samples, bound, edges)
+    d = torch.as_tensor(denom, device=counts.device)
+    g = torch.empty(denom.shape[0], dtype=torch.float64, device=counts.device)
+    _lib.check(_lib.load().fs_rdf_mean(_lib.ptr(counts), counts.shape[0], counts.shape[1], _lib.ptr(d), _lib.ptr(g),
+                                       _lib.stream_ptr()), "fs_rdf_mean")
+    return r_vals, pd.Series(g.cpu().numpy())
+
+
+def _rdf_bins(n_particles, bound, dr):
+    """calculate_pair_correlation's edges, normalisation and r values (utils.py:559-572)."""
+    edges = np.arange(0, bound + dr, dr)
     norm = n_particles * (n_particles - 1) / 2
     rou = n_particles / (4 * bound * bound)
     i_vals = np.arange(0, bound, dr)
     area = np.pi * ((i_vals + dr) ** 2 - i_vals ** 2)
     denom = norm * rou * area
-    if denom.shape[0] != counts.shape[1]:
-        raise ValueError(f"operands could not be broadcast together with shapes ({counts.shape[1]},) ({denom.shape[0]},)")
-    d = torch.as_tensor(denom, device=counts.device)
-    g = torch.empty(denom.shape[0], dtype=torch.float64, device=counts.device)
-    _lib.check(_lib.load().fs_rdf_mean(_lib.ptr(counts), counts.shape[0], counts.shape[1], _lib.ptr(d), _lib.ptr(g),
-                                       _lib.stream_ptr()), "fs_rdf_mean")
-    return np.arange(0, bound, dr), pd.Series(g.cpu().numpy())
+    if denom.shape[0] != edges.shape[0] - 1:
+        raise ValueError(f"operands could not be broadcast together with shapes ({edges.shape[0] - 1},) "
+                         f"({denom.shape[0]},)")
+    return edges, denom, np.arange(0, bound, dr)
+
+
+def sample_analysis_batch(z, half_box, hist_edges, r_edges, samples_out, hist, counts):
+    """fs_sample_analysis on one batch: z (M, N, 2) float32 device samples in centred
+    coordinates; samples_out (M, N, 2) float32, hist (nb, nb) int64 (accumulated) and
+    counts (M, nr) int32 are written in place (contiguous device tensors / row slices)."""
+    M, N, _ = z.shape
+    _lib.require_device(z, hist_edges, r_edges, samples_out, hist, counts)
+    if z.dtype != torch.float32 or not z.is_contiguous():
+        raise ValueError("sample_analysis_batch: z must be a contiguous float32 (M, N, 2) tensor")
+    if not (samples_out.is_contiguous() and hist.is_contiguous() and counts.is_contiguous()):
+        raise ValueError("sample_analysis_batch: outputs must be contiguous")
+    if samples_out.shape != z.shape or counts.shape != (M, r_edges.numel() - 1) or \
+            hist.numel() != (hist_edges.numel() - 1) ** 2:
+        raise ValueError("sample_analysis_batch: output shapes do not match the batch")
+    _lib.check(_lib.load().fs_sample_analysis(_lib.ptr(z), M, N, float(half_box), _lib.ptr(hist_edges),
+                                              hist_edges.numel() - 1, _lib.ptr(r_edges), r_edges.numel() - 1,
+                                              _lib.ptr(samples_out), _lib.ptr(hist), _lib.ptr(counts),
+                                              _lib.stream_ptr()), "fs_sample_analysis")
+
+
+def sample_analysis(model, n_samples, half_box, batch=1000, bins=100, dr=None, generator=None):
+    """The analysis batch of an Algorithm-2 checkpoint cycle (main_algorithm_2.py:485-525)
+    on the device: ceil(n_samples / batch) batches of model.sample(batch) in eval mode
+    (all n_iterations * batch rows are kept, as the reference keeps them), each through
+    one fs_sample_analysis launch, then g(r) by one fs_rdf_mean; no host synchronisation
+    until the results are copied out.  The base draws are made on the model's device
+    (q0's uniform on [-bound, bound], `generator`: a device torch.Generator, default the
+    device's own), so the host generator that orders the training batches is untouched.
+    Returns a dict: samples (n, N, 2) float32 device tensor (the rows of samples.npy),
+    hist (nb, nb) int64, x_edges / y_edges (np.linspace(-bound, bound, bins)), r_vals,
+    g_r (numpy)."""
+    half_box = float(half_box)
+    if dr is None:
+        dr = half_box / 50
+    dev = next(model.parameters()).device
+    N, dim = model.q0.n_particles, model.q0.n_dimension
+    if dim != 2:
+        raise ValueError("sample_analysis: two-dimensional particles only")
+    n_iter = (int(n_samples) + batch - 1) // batch
+    total = n_iter * batch
+    x_edges = np.linspace(-half_box, half_box, bins)
+    r_edges, denom, r_vals = _rdf_bins(N, half_box, dr)
+    nb, nr = bins - 1, r_edges.shape[0] - 1
+    was_training = model.training
+    if was_training:
+        model.eval()
+    with _lib.on_device(dev), torch.no_grad():
+        e2 = torch.as_tensor(x_edges, device=dev)
+        er = torch.as_tensor(r_edges, device=dev)
+        d = torch.as_tensor(denom, device=dev)
+        samples = torch.empty((total, N, 2), dtype=torch.float32, device=dev)
+        hist = torch.zeros((nb, nb), dtype=torch.int64, device=dev)
+        counts = torch.empty((total, nr), dtype=torch.int32, device=dev)
+        g = torch.empty(nr, dtype=torch.float64, device=dev)
+        bound = float(model.q0.bound)
+        for i in range(n_iter):
+            u = torch.empty((batch, N * 2), dtype=torch.float32, device=dev).uniform_(-bound, bound,
+                                                                                       generator=generator)
+            z = model.forward(u).reshape(batch, N, 2).contiguous()
+            sample_analysis_batch(z, half_box, e2, er, samples[i * batch:(i + 1) * batch], hist,
+                                  counts[i * batch:(i + 1) * batch])
+        if total:
+            _lib.check(_lib.load().fs_rdf_mean(_lib.ptr(counts), total, nr, _lib.ptr(d), _lib.ptr(g),
+                                               _lib.stream_ptr()), "fs_rdf_mean")
+    if was_training:
+        model.train()
+    return {"samples": samples, "hist": hist, "x_edges": x_edges, "y_edges": x_edges.copy(), "r_vals": r_vals,
+            "g_r": g.cpu().numpy()}
 
 
 def generate_samples(model, n_particles, n_dimension, n_iterations=100, samples_per_iteration=5000,

@@ -9,6 +9,15 @@ written from the batched engine's device results:
   acceptance_rate_data.csv main_algorithm_1.py:434-440
   model .pth               torch.save(model.state_dict()) (main_algorithm_1.py:327)
 
+and of the Algorithm-2 driver's checkpoint cycles (hybrid_NF_MCMC/main_algorithm_2.py):
+
+  samples.npy                                    main_algorithm_2.py:504-505
+  frequency_heatmap_cycle_{c}_data.json          utils.py:495-506
+  pair_correlation_function_{c}_data.json        utils.py:599-606
+  loss_function_data.json                        utils.py:403-406
+  model_checkpoint_cycle_{c}.pth                 main_algorithm_2.py:468-470
+  p_acc_history_data.json                        main_algorithm_2.py:588-599
+
 The batched engine returns sample() snapshots as device arrays (E, W and the
 configuration at each sampled step); `sample_tuples` turns one chain's snapshots
 into the reference's tuples with the reference's arithmetic.
@@ -72,6 +81,74 @@ def write_acceptance_rate(path, steps_history, p_acc_history):
         w.writerow(["MCMC_Steps", "Acceptance_Rate"])
         for s, a in zip(steps_history, p_acc_history):
             w.writerow([s, a])
+
+
+# ---------------------------------------------------------------- Algorithm 2
+# The data files of main_algorithm_2.py's checkpoint cycles (the reference writes each
+# next to a plot; the plots stay out of scope).
+
+def _tolist(a):
+    return a.tolist() if hasattr(a, "tolist") else list(a)
+
+
+def save_samples(directory, samples):
+    """samples.npy (main_algorithm_2.py:504-505): the analysis batch, float32 (n, N, 2)."""
+    a = samples.cpu().numpy() if hasattr(samples, "cpu") else np.asarray(samples)
+    path = os.path.join(directory, "samples.npy")
+    np.save(path, a)
+    return path
+
+
+def write_frequency_heatmap(directory, cycle, hist, x_edges, y_edges, cmap_name=None):
+    """frequency_heatmap_cycle_{cycle}_data.json (utils.py:495-506): the histogram2d
+    counts normalised in float64."""
+    hist = (hist.cpu().numpy() if hasattr(hist, "cpu") else np.asarray(hist)).astype(np.float64)
+    data = {"hist_relative": (hist / hist.sum()).tolist(), "x_edges": _tolist(x_edges), "y_edges": _tolist(y_edges),
+            "cmap_name": cmap_name}
+    path = os.path.join(directory, f"frequency_heatmap_cycle_{cycle}_data.json")
+    with open(path, "w") as f:
+        json.dump(data, f)
+    return path
+
+
+def write_pair_correlation(directory, cycle, r_vals, g_r):
+    """pair_correlation_function_{cycle}_data.json (utils.py:599-606); `directory` is stored
+    with the trailing separator the reference passes."""
+    g = g_r.values if hasattr(g_r, "values") else g_r
+    data = {"r": _tolist(r_vals), "g_r": _tolist(g), "directory": str(directory) + "/"}
+    path = os.path.join(directory, f"pair_correlation_function_{cycle}_data.json")
+    with open(path, "w") as f:
+        json.dump(data, f)
+    return path
+
+
+def save_model_checkpoint(directory, cycle, model):
+    """model_checkpoint_cycle_{cycle}.pth (main_algorithm_2.py:469-470)."""
+    import torch
+
+    path = os.path.join(directory, f"model_checkpoint_cycle_{cycle}.pth")
+    torch.save(model.state_dict(), path)
+    return path
+
+
+def write_loss_history(directory, loss_epoch, base_filename="loss_function"):
+    """loss_function_data.json (utils.py:403-406)."""
+    path = os.path.join(directory, f"{base_filename}_data.json")
+    with open(path, "w") as f:
+        json.dump({"loss_epoch": _tolist(loss_epoch)}, f)
+    return path
+
+
+def write_p_acc_history(directory, p_acc_history, initial_training_num_samples, update_num_samples):
+    """p_acc_history_data.json (main_algorithm_2.py:588-599): p_acc_history is the initial
+    acceptance followed by one entry per cycle; total_samples_trained has as many entries."""
+    total = [initial_training_num_samples]
+    for _ in range(1, len(p_acc_history)):
+        total.append(total[-1] + update_num_samples)
+    path = os.path.join(directory, "p_acc_history_data.json")
+    with open(path, "w") as f:
+        json.dump({"total_samples_trained": total, "p_acc_history": list(p_acc_history)}, f, indent=4)
+    return path
 
 
 def write_run_dir(run_dir, local_samples, testing_samples=None):

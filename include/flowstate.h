@@ -695,6 +695,25 @@ int fs_pair_hist(const void *pos, int pos_is_f32, int64_t M, int32_t N, double b
  * pairwise sum / M).  g_r [nbins] f64. */
 int fs_rdf_mean(const int32_t *counts, int64_t M, int32_t nbins, const double *denom, double *g_r, void *stream);
 
+/* One analysis batch of the Algorithm-2 checkpoint cycle
+ * (main_algorithm_2.py:493-525) in one launch.  z [M][N][2] float32 flow samples
+ * in centred coordinates; everything is float32 as in the reference's numpy
+ * arrays, HALF_BOX rounded to float32 (weak Python scalar), no contraction:
+ *   samples_out [M][N][2] = z + (float)half_box         (the rows of samples.npy)
+ *   c = samples_out - (float)half_box                   (what the reference analyses)
+ *   hist [nbins][nbins] int64 += np.histogram2d of c, each coordinate widened to
+ *     float64 against hist_edges [nbins+1] (fs_hist2d's rule, hist[bx*nbins+by]);
+ *     accumulated across calls, the caller zeroes it once per checkpoint
+ *   counts [M][r_nbins] int32 = the pair-distance counts of c per configuration
+ *     against r_edges [r_nbins+1], fs_pair_hist's float32 arithmetic with
+ *     bound = half_box (overwritten; pass the batch's row of a larger buffer).
+ * g(r) over all rows is fs_rdf_mean of the counts.  Limits: N <= 256,
+ * nbins <= 120, r_nbins <= 128 (FS_EINVAL otherwise, nothing launched);
+ * M = 0 is a no-op. */
+int fs_sample_analysis(const float *z, int64_t M, int32_t N, double half_box, const double *hist_edges, int32_t nbins,
+                       const double *r_edges, int32_t r_nbins, float *samples_out, int64_t *hist, int32_t *counts,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
