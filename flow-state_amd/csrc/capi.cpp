@@ -487,6 +487,27 @@ int fs_rqs_backward(int64_t M, int32_t K, int32_t inverse, const float *x, const
                   "fs_rqs_backward");
 }
 
+int fs_rqs_forward_any(int64_t M, int32_t K, int32_t inverse, const float *x, const float *uw, const float *uh,
+                       const float *ud, double tail_bound, float *out, float *lad, int32_t *nan_flag, void *stream) {
+    REQUIRE(M >= 0 && tail_bound > 0 && (M == 0 || (x && uw && uh && ud && out && lad)),
+            "fs_rqs_forward_any: invalid arguments");
+    REQUIRE(K >= 1 && K <= 32, "fs_rqs_forward_any: K=%d outside 1..32", K);
+    return hip_rc(fs_rqs_forward_any_impl(M, K, inverse, x, uw, uh, ud, (float)tail_bound, out, lad, nan_flag,
+                                          (hipStream_t)stream),
+                  "fs_rqs_forward_any");
+}
+
+int fs_rqs_backward_any(int64_t M, int32_t K, int32_t inverse, const float *x, const float *uw, const float *uh,
+                        const float *ud, double tail_bound, const float *g_out, const float *g_lad, float *gx,
+                        float *guw, float *guh, float *gud, void *stream) {
+    REQUIRE(M >= 0 && tail_bound > 0 && (M == 0 || (x && uw && uh && ud && gx && guw && guh && gud)),
+            "fs_rqs_backward_any: invalid arguments");
+    REQUIRE(K >= 1 && K <= 32, "fs_rqs_backward_any: K=%d outside 1..32", K);
+    return hip_rc(fs_rqs_backward_any_impl(M, K, inverse, x, uw, uh, ud, (float)tail_bound, g_out, g_lad, gx, guw,
+                                           guh, gud, (hipStream_t)stream),
+                  "fs_rqs_backward_any");
+}
+
 int64_t fs_set_wide_rows(int64_t rows) { return fs_set_wide_rows_impl(rows); }
 int32_t fs_set_wide_trunk16(int32_t on) { return fs_set_wide_trunk16_impl(on); }
 int32_t fs_set_wide_final32(int32_t on) { return fs_set_wide_final32_impl(on); }

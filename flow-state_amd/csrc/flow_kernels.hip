@@ -2402,10 +2402,13 @@ extern "C" int fs_prof_read(unsigned long long *out, int reset) {
 
 bool fs_flow_supported(const fs_flow_dims *d, char *why, size_t n) {
     if (!d) return false;
-    if (d->precision < 0 || d->precision > 2) {
-        snprintf(why, n, "precision %d: 0 (f32 MFMA), 1 (bf16x6 split) or 2 (bf16x3 split)", d->precision);
+    // 3 is not a mode: it stays the rejected value it has always been (tests/test_host_precision.py)
+    if (d->precision < 0 || d->precision > 4 || d->precision == 3) {
+        snprintf(why, n, "precision %d: 0 (f32 MFMA), 1 (bf16x6 split), 2 (bf16x3 split) or 4 (f32, general shape)",
+                 d->precision);
         return false;
     }
+    if (d->precision == 4) return fs_flow_general_supported(d, why, n);
     if (d->precision != 0 && !fs_flow_split_supported(d, why, n)) return false;
     bool ok_hk = d->precision != 0;
 #define FS_CASE(HH, KK) ok_hk |= (d->H == HH && d->K == KK);
@@ -2413,7 +2416,8 @@ bool fs_flow_supported(const fs_flow_dims *d, char *why, size_t n) {
 #undef FS_CASE
     if (!ok_hk) {
         snprintf(why, n, "unsupported (H=%d, K=%d): instantiated (H, K) pairs are listed in FS_FLOW_INSTANCES "
-                 "(flow_kernels.hip)", d->H, d->K);
+                 "(flow_kernels.hip). The general-shape mode (precision 4, \"f32-general\") runs any H <= 512, "
+                 "K <= 32.", d->H, d->K);
         return false;
     }
     if (d->N < 1 || d->N > kMaxN || d->L < 1 || d->nb < 0 || d->K < 1 || d->K > kMaxK || !(d->tail_bound > 0)) {
@@ -2438,6 +2442,7 @@ int64_t fs_flow_raw_floats_impl(const fs_flow_dims *d) {
 }
 
 int64_t fs_flow_packed_bytes_impl(const fs_flow_dims *d) {
+    if (d->precision == 4) return fs_flow_general_packed_bytes(d);
     if (d->precision != 0) return fs_flow_split_packed_bytes(d);
     return pack_layout(d->N, d->H, d->nb, d->K).stride * d->L * 4;
 }
@@ -2467,6 +2472,7 @@ hipError_t fs_flow_pack_vec(float *dst, const float *raw_layer, const fs_flow_di
 }
 
 hipError_t fs_flow_pack_impl(const fs_flow_dims *d, const float *raw, float *packed, hipStream_t st) {
+    if (d->precision == 4) return fs_flow_general_pack(d, raw, packed, st);
     if (d->precision != 0) return fs_flow_split_pack(d, raw, packed, st);
     const int N = d->N, H = d->H, nb = d->nb, K = d->K;
     const RawLayout R = raw_layout(N, H, nb, K);
@@ -2547,6 +2553,7 @@ hipError_t fs_flow_pass_impl(const fs_flow_dims *d, const void *packed, int mode
     a.rows_per_counter = rows_per_counter;
     a.half_width = half_width;
     a.err = err;
+    if (d->precision == 4) return fs_flow_general_pass(a, mode, d->N, d->H, d->K, st);
     if (d->precision != 0) return fs_flow_split_pass(a, mode, d->precision, d->N, d->H, d->K, st);
     if (B <= wide_rows_limit() && (B + kRows - 1) / kRows < 2 * 256) {
         // small batch: the wide path (bit-identical results), when its workspace is available

@@ -26,6 +26,12 @@ bool fs_flow_split_supported(const fs_flow_dims *d, char *why, size_t n);
 int64_t fs_flow_split_packed_bytes(const fs_flow_dims *d);
 hipError_t fs_flow_split_pack(const fs_flow_dims *d, const float *raw, float *packed, hipStream_t st);
 hipError_t fs_flow_split_pass(const fs::FlowArgs &a, int mode, int precision, int N, int H, int K, hipStream_t st);
+// general-shape f32 flow image and pass (flow_general_kernels.hip; fs_flow_dims.precision 4):
+// any H <= 512, K <= 32 on one runtime-shaped kernel per pass mode
+bool fs_flow_general_supported(const fs_flow_dims *d, char *why, size_t n);
+int64_t fs_flow_general_packed_bytes(const fs_flow_dims *d);
+hipError_t fs_flow_general_pack(const fs_flow_dims *d, const float *raw, float *packed, hipStream_t st);
+hipError_t fs_flow_general_pass(const fs::FlowArgs &a, int mode, int N, int H, int K, hipStream_t st);
 // pack_vec_kernel of the f32 image (biases, folded BatchNorm, unconditional knots), launched
 // with dst shifted so that its vector section lands where the caller's image keeps it
 hipError_t fs_gather_chunks_impl(const int64_t *tab, int64_t n, float *dst, hipStream_t st);
@@ -61,6 +67,13 @@ hipError_t fs_rqs_forward_impl(int64_t M, int K, int inverse, const float *x, co
 hipError_t fs_rqs_backward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
                                 const float *ud, float B, const float *g_out, const float *g_lad, float *gx,
                                 float *guw, float *guh, float *gud, hipStream_t st);
+// the same on runtime-K kernels, any 1 <= K <= 32
+hipError_t fs_rqs_forward_any_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
+                                   const float *ud, float B, float *out, float *lad, int32_t *nan_flag,
+                                   hipStream_t st);
+hipError_t fs_rqs_backward_any_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
+                                    const float *ud, float B, const float *g_out, const float *g_lad, float *gx,
+                                    float *guw, float *guh, float *gud, hipStream_t st);
 int64_t fs_set_wide_rows_impl(int64_t rows);
 int32_t fs_set_wide_trunk16_impl(int32_t on);
 int32_t fs_set_wide_final32_impl(int32_t on);

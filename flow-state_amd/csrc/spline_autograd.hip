@@ -326,6 +326,236 @@ __global__ __launch_bounds__(256) void rqs_backward_kernel(int64_t M, const floa
     for (int k = 0; k <= K; ++k) gud[i * (K + 1) + k] = d[k];
 }
 
+// ---------------------------------------------------------------------------
+// The same two kernels with K a run-time value, 1 <= K <= kAnyMaxK (fs_rqs_forward_any /
+// fs_rqs_backward_any): the operations of build_knots, find_bin, rqs_eval_knots,
+// rqs_bwd_core and knots_backward in the same order, on arrays of kAnyMaxK with K as the
+// loop bound (they live in private memory, so a bin is a plain index).
+constexpr int kAnyMaxK = 32;
+
+struct KnotsAny {
+    float c[kAnyMaxK + 1];
+    float p[kAnyMaxK];
+};
+
+__device__ __forceinline__ void build_knots_any(int K, const float *u, float B, KnotsAny &kn) {
+    float m = u[0];
+    for (int k = 1; k < K; ++k) m = fmaxf(m, u[k]);
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) {
+        kn.p[k] = expf(u[k] - m);
+        s += kn.p[k];
+    }
+    for (int k = 0; k < K; ++k) kn.p[k] = kn.p[k] / s;
+    const float c1 = 1.f - kMin * (float)K;
+    double cs = 0.0;
+    kn.c[0] = -B;
+    for (int k = 0; k < K - 1; ++k) {
+        cs += (double)(kMin + c1 * kn.p[k]);
+        kn.c[k + 1] = (2.f * B) * (float)cs + (-B);
+    }
+    kn.c[K] = B;
+}
+
+__device__ __forceinline__ int find_bin_any(int K, float x, const float *knots) {
+    int b = -1;
+    for (int k = 0; k <= K; ++k) {
+        const float kv = (k == K) ? knots[K] + 1e-6f : knots[k];
+        b += (x >= kv) ? 1 : 0;
+    }
+    return b < 0 ? 0 : (b > K - 1 ? K - 1 : b);
+}
+
+template <bool INV>
+__device__ __forceinline__ void rqs_point_any(int K, float xv, const float *uw, const float *uh, const float *dd,
+                                              float B, float &out, float &lad, int32_t *nan_flag) {
+    KnotsAny W, Hh;
+    build_knots_any(K, uw, B, W);
+    build_knots_any(K, uh, B, Hh);
+    const float *wc = W.c, *hc = Hh.c;
+    const int b = find_bin_any(K, xv, INV ? hc : wc);
+    const float d0 = kMin + softplus(dd[b]), d1 = kMin + softplus(dd[b + 1]);
+    const float icw = wc[b], cw1 = wc[b + 1], ich = hc[b], ch1 = hc[b + 1];
+    const float ibw = cw1 - icw, ih = ch1 - ich;
+    const float s = ih / ibw;
+    float th;
+    if (INV) {
+        const float sdd = d0 + d1 - 2.f * s;
+        const float a = (xv - ich) * sdd + ih * (s - d0);
+        const float bb = ih * d0 - (xv - ich) * sdd;
+        const float c = -s * (xv - ich);
+        const float disc = fabsf(bb * bb - 4.f * a * c);
+        if (disc != disc && nan_flag) atomicOr(nan_flag, 1);
+        th = (2.f * c) / (-bb - sqrtf(disc));
+    } else {
+        th = (xv - icw) / ibw;
+    }
+    const float t = th * (1.f - th);
+    const float den = s + (d0 + d1 - 2.f * s) * t;
+    const float A = d1 * th * th + 2.f * s * t + d0 * (1.f - th) * (1.f - th);
+    const float l = logf(s * s * A) - 2.f * logf(den);
+    if (INV) {
+        out = th * ibw + icw;
+        lad = -l;
+    } else {
+        out = ich + ih * (s * th * th + d0 * t) / den;
+        lad = l;
+    }
+}
+
+template <bool INV>
+__global__ __launch_bounds__(256) void rqs_forward_any_kernel(int64_t M, int K, const float *__restrict__ x,
+                                                              const float *__restrict__ uw,
+                                                              const float *__restrict__ uh,
+                                                              const float *__restrict__ ud, float B,
+                                                              float *__restrict__ out, float *__restrict__ lad,
+                                                              int32_t *__restrict__ nan_flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    const float xv = x[i];
+    if (!(xv >= -B && xv <= B)) {
+        out[i] = xv;
+        lad[i] = 0.f;
+        return;
+    }
+    rqs_point_any<INV>(K, xv, uw + i * K, uh + i * K, ud + i * (K + 1), B, out[i], lad[i], nan_flag);
+}
+
+// knot adjoints (g_b at knot b, g_b1 at knot b + 1, zero elsewhere) -> unnormalised-parameter
+// adjoints: knots_backward on that sparse gc
+__device__ __forceinline__ void knots_backward_any(int K, const KnotsAny &kn, int b, float g_b, float g_b1, float B,
+                                                   float *gu) {
+    const float c1 = 1.f - kMin * (float)K;
+    float gw[kAnyMaxK];
+    float suffix = 0.f;
+    for (int j = K - 1; j >= 0; --j) {
+        gw[j] = suffix;
+        const float gcj = (j == b) ? g_b : ((j == b + 1) ? g_b1 : 0.f);
+        if (j >= 1) suffix += (2.f * B) * gcj;
+    }
+    float dot = 0.f;
+    for (int j = 0; j < K; ++j) dot += kn.p[j] * (c1 * gw[j]);
+    for (int j = 0; j < K; ++j) gu[j] = kn.p[j] * (c1 * gw[j] - dot);
+}
+
+template <bool INV>
+__global__ __launch_bounds__(256) void rqs_backward_any_kernel(int64_t M, int K, const float *__restrict__ x,
+                                                               const float *__restrict__ uw,
+                                                               const float *__restrict__ uh,
+                                                               const float *__restrict__ ud, float B,
+                                                               const float *__restrict__ g_out,
+                                                               const float *__restrict__ g_lad,
+                                                               float *__restrict__ gx, float *__restrict__ guw,
+                                                               float *__restrict__ guh, float *__restrict__ gud) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    const float xv = x[i];
+    const float go = g_out ? g_out[i] : 0.f, gl = g_lad ? g_lad[i] : 0.f;
+    float *pw = guw + i * K, *ph = guh + i * K, *pd = gud + i * (K + 1);
+    if (!(xv >= -B && xv <= B)) {
+        gx[i] = go;
+        for (int k = 0; k < K; ++k) {
+            pw[k] = 0.f;
+            ph[k] = 0.f;
+        }
+        for (int k = 0; k <= K; ++k) pd[k] = 0.f;
+        return;
+    }
+    KnotsAny W, Hh;
+    build_knots_any(K, uw + i * K, B, W);
+    build_knots_any(K, uh + i * K, B, Hh);
+    const float *wc = W.c, *hc = Hh.c, *dd = ud + i * (K + 1);
+    // rqs_bwd_core
+    const int b = find_bin_any(K, xv, INV ? hc : wc);
+    const float e0 = dd[b], e1 = dd[b + 1];
+    const float d0 = kMin + softplus(e0), d1 = kMin + softplus(e1);
+    const float icw = wc[b], cw1 = wc[b + 1], ich = hc[b], ch1 = hc[b + 1];
+    const float ibw = cw1 - icw, ih = ch1 - ich;
+    const float s = ih / ibw;
+    float th;
+    if (INV) {
+        const float sdd = d0 + d1 - 2.f * s;
+        const float a = (xv - ich) * sdd + ih * (s - d0);
+        const float bb = ih * d0 - (xv - ich) * sdd;
+        const float c = -s * (xv - ich);
+        const float disc = fabsf(bb * bb - 4.f * a * c);
+        th = (2.f * c) / (-bb - sqrtf(disc));
+    } else {
+        th = (xv - icw) / ibw;
+    }
+    const float t = th * (1.f - th);
+    const float omt = 1.f - th;
+    const float Nn = s * th * th + d0 * t;
+    const float den = s + (d0 + d1 - 2.f * s) * t;
+    const float A = d1 * th * th + 2.f * s * t + d0 * omt * omt;
+    const float dnum = s * s * A;
+    float g_th = 0.f, g_s = 0.f, g_t = 0.f, g_d0 = 0.f, g_d1 = 0.f;
+    float g_icw = 0.f, g_ibw = 0.f, g_ich = 0.f, g_ih = 0.f, g_x = 0.f;
+    const float gll = INV ? -gl : gl;
+    {
+        const float g_dnum = gll / dnum;
+        const float g_den = -2.f * gll / den;
+        const float g_A = g_dnum * s * s;
+        g_s += g_dnum * 2.f * s * A + g_A * 2.f * t;
+        g_d1 += g_A * th * th;
+        g_d0 += g_A * omt * omt;
+        g_th += g_A * (2.f * d1 * th - 2.f * d0 * omt);
+        g_t += g_A * 2.f * s;
+        g_s += g_den * (1.f - 2.f * t);
+        g_d0 += g_den * t;
+        g_d1 += g_den * t;
+        g_t += g_den * (d0 + d1 - 2.f * s);
+    }
+    if (INV) {
+        g_th += go * ibw;
+        g_icw += go;
+        g_ibw += go * th;
+        g_th += g_t * (1.f - 2.f * th);
+        const float N_th = 2.f * s * th + d0 * (1.f - 2.f * th);
+        const float den_th = (d0 + d1 - 2.f * s) * (1.f - 2.f * th);
+        const float F_th = ih * (N_th * den - Nn * den_th) / (den * den);
+        const float F_s = ih * (th * th * den - Nn * (1.f - 2.f * t)) / (den * den);
+        const float F_d0 = ih * (t * den - Nn * t) / (den * den);
+        const float F_d1 = -ih * Nn * t / (den * den);
+        const float wgt = g_th / F_th;
+        g_x += wgt;
+        g_ich -= wgt;
+        g_ih -= wgt * Nn / den;
+        g_s -= wgt * F_s;
+        g_d0 -= wgt * F_d0;
+        g_d1 -= wgt * F_d1;
+    } else {
+        const float g_num = go / den;
+        const float g_den = -go * (ih * Nn) / (den * den);
+        g_ich += go;
+        g_ih += g_num * Nn;
+        const float g_N = g_num * ih;
+        g_s += g_N * th * th;
+        g_th += g_N * 2.f * s * th;
+        g_d0 += g_N * t;
+        g_t += g_N * d0;
+        g_s += g_den * (1.f - 2.f * t);
+        g_d0 += g_den * t;
+        g_d1 += g_den * t;
+        g_t += g_den * (d0 + d1 - 2.f * s);
+        g_th += g_t * (1.f - 2.f * th);
+        g_x += g_th / ibw;
+        g_icw -= g_th / ibw;
+        g_ibw -= g_th * th / ibw;
+    }
+    g_ih += g_s / ibw;
+    g_ibw -= g_s * s / ibw;
+    gx[i] = g_x;
+    for (int k = 0; k <= K; ++k) {
+        float g = 0.f;
+        if (k == b) g = g_d0 * softplus_grad(e0);
+        if (k == b + 1) g = g_d1 * softplus_grad(e1);
+        pd[k] = g;
+    }
+    knots_backward_any(K, W, b, g_icw - g_ibw, g_ibw, B, pw);
+    knots_backward_any(K, Hh, b, g_ich - g_ih, g_ih, B, ph);
+}
+
 
 // ---------------------------------------------------------------------------
 // One coupling layer of the training path around its conditioner: the feature gather,
@@ -1040,6 +1270,36 @@ hipError_t fs_rqs_backward_impl(int64_t M, int K, int inverse, const float *x, c
     FS_RQS_K(FS_B)
 #undef FS_B
     return hipErrorInvalidValue;
+}
+
+hipError_t fs_rqs_forward_any_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
+                                   const float *ud, float B, float *out, float *lad, int32_t *nan_flag,
+                                   hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    if (K < 1 || K > kAnyMaxK) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    if (inverse)
+        hipLaunchKernelGGL(rqs_forward_any_kernel<true>, grid, block, 0, st, M, K, x, uw, uh, ud, B, out, lad,
+                           nan_flag);
+    else
+        hipLaunchKernelGGL(rqs_forward_any_kernel<false>, grid, block, 0, st, M, K, x, uw, uh, ud, B, out, lad,
+                           nan_flag);
+    return hipGetLastError();
+}
+
+hipError_t fs_rqs_backward_any_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
+                                    const float *ud, float B, const float *g_out, const float *g_lad, float *gx,
+                                    float *guw, float *guh, float *gud, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    if (K < 1 || K > kAnyMaxK) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    if (inverse)
+        hipLaunchKernelGGL(rqs_backward_any_kernel<true>, grid, block, 0, st, M, K, x, uw, uh, ud, B, g_out, g_lad,
+                           gx, guw, guh, gud);
+    else
+        hipLaunchKernelGGL(rqs_backward_any_kernel<false>, grid, block, 0, st, M, K, x, uw, uh, ud, B, g_out, g_lad,
+                           gx, guw, guh, gud);
+    return hipGetLastError();
 }
 
 // the training step's coupling launches on two / four waves per row (1, default, or

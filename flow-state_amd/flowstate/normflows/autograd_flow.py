@@ -183,7 +183,7 @@ class _CircularRQS(torch.autograd.Function):
     fs_rqs_forward / fs_rqs_backward) instead of ~100 small torch kernels."""
 
     @staticmethod
-    def forward(ctx, x, uw, uh, ud, B, inverse):
+    def forward(ctx, x, uw, uh, ud, B, inverse, any_k=False):
         from .. import _lib
 
         x, uw, uh, ud = (t.detach().contiguous().float() for t in (x, uw, uh, ud))
@@ -192,11 +192,13 @@ class _CircularRQS(torch.autograd.Function):
         lad = torch.empty_like(x)
         flag = torch.zeros(1, dtype=torch.int32, device=x.device)
         L = _lib.load()
+        # an uninstantiated bin count on the runtime-K kernels (fs_rqs_*_any)
+        ctx.any_k = bool(any_k) and K not in _HIP_K
+        fwd = L.fs_rqs_forward_any if ctx.any_k else L.fs_rqs_forward
         with _lib.on_device(x):
             _lib.require_device(x, uw, uh, ud)
-            _lib.check(L.fs_rqs_forward(M, K, int(inverse), _lib.ptr(x), _lib.ptr(uw), _lib.ptr(uh), _lib.ptr(ud),
-                                        float(B), _lib.ptr(out), _lib.ptr(lad), _lib.ptr(flag), _lib.stream_ptr()),
-                       "fs_rqs_forward")
+            _lib.check(fwd(M, K, int(inverse), _lib.ptr(x), _lib.ptr(uw), _lib.ptr(uh), _lib.ptr(ud), float(B),
+                           _lib.ptr(out), _lib.ptr(lad), _lib.ptr(flag), _lib.stream_ptr()), "fs_rqs_forward")
         _nan_flags.append(flag[0] != 0)
         ctx.save_for_backward(x, uw, uh, ud)
         ctx.B, ctx.inverse = float(B), int(inverse)
@@ -215,21 +217,24 @@ class _CircularRQS(torch.autograd.Function):
         guh = torch.empty_like(uh)
         gud = torch.empty_like(ud)
         L = _lib.load()
+        bwd = L.fs_rqs_backward_any if ctx.any_k else L.fs_rqs_backward
         with _lib.on_device(x):
             _lib.require_device(x, go, gl)
-            _lib.check(L.fs_rqs_backward(M, K, ctx.inverse, _lib.ptr(x), _lib.ptr(uw), _lib.ptr(uh), _lib.ptr(ud),
-                                         ctx.B, _lib.ptr(go), _lib.ptr(gl), _lib.ptr(gx), _lib.ptr(guw),
-                                         _lib.ptr(guh), _lib.ptr(gud), _lib.stream_ptr()), "fs_rqs_backward")
-        return gx, guw, guh, gud, None, None
+            _lib.check(bwd(M, K, ctx.inverse, _lib.ptr(x), _lib.ptr(uw), _lib.ptr(uh), _lib.ptr(ud), ctx.B,
+                           _lib.ptr(go), _lib.ptr(gl), _lib.ptr(gx), _lib.ptr(guw), _lib.ptr(guh), _lib.ptr(gud),
+                           _lib.stream_ptr()), "fs_rqs_backward")
+        return gx, guw, guh, gud, None, None, None
 
 
-def circular_rqs(x, uw, uh, ud, B, inverse):
+def circular_rqs(x, uw, uh, ud, B, inverse, any_k=False):
     """Dispatch: the fused HIP spline for device tensors, the torch restatement below for
     CPU tensors (tests and host-side use).  A device tensor with a bin count K the HIP
     spline does not instantiate raises (DESIGN.md 'The path and its boundary': unsupported
-    options raise instead of computing something else)."""
+    options raise instead of computing something else), unless any_k: then such a K
+    (1 <= K <= 32) runs on the runtime-K kernels fs_rqs_forward_any / fs_rqs_backward_any
+    (the general-shape mode's training spline)."""
     if x.is_cuda:
-        if uw.shape[-1] not in _HIP_K:
+        if uw.shape[-1] not in _HIP_K and not (any_k and 1 <= uw.shape[-1] <= 32):
             from .. import _lib
 
             raise _lib.FlowStateError(f"the HIP spline is instantiated for K in {sorted(_HIP_K)}, "
@@ -237,7 +242,7 @@ def circular_rqs(x, uw, uh, ud, B, inverse):
         shp = x.shape
         K = uw.shape[-1]
         out, lad = _CircularRQS.apply(x.reshape(-1), uw.reshape(-1, K), uh.reshape(-1, K), ud.reshape(-1, K + 1),
-                                      B, inverse)
+                                      B, inverse, any_k)
         return out.reshape(shp), lad.reshape(shp)
     return circular_rqs_torch(x, uw, uh, ud, B, inverse)
 
@@ -856,8 +861,13 @@ def _cond_spline(layer, trans, params, inverse):
     uw = params[..., :K] / sq
     uh = params[..., K:2 * K] / sq
     ud = params[..., 2 * K:]
-    out, lad = circular_rqs(trans, uw, uh, ud, layer.tail_bound, inverse)
+    out, lad = circular_rqs(trans, uw, uh, ud, layer.tail_bound, inverse, any_k=_any_k(layer))
     return out, lad.sum(dim=1)
+
+
+def _any_k(layer):
+    """The layer is in the general-shape mode: its splines may take any bin count."""
+    return getattr(layer, "_fs_precision", "f32") == "f32-general"
 
 
 def _uncond_spline(layer, ident, inverse):
@@ -866,7 +876,7 @@ def _uncond_spline(layer, ident, inverse):
     uw = u.unnormalized_widths[None].expand(n, *u.unnormalized_widths.shape)
     uh = u.unnormalized_heights[None].expand(n, *u.unnormalized_heights.shape)
     ud = u.unnormalized_derivatives[None].expand(n, *u.unnormalized_derivatives.shape)
-    out, lad = circular_rqs(ident, uw, uh, ud, layer.tail_bound, inverse)
+    out, lad = circular_rqs(ident, uw, uh, ud, layer.tail_bound, inverse, any_k=_any_k(layer))
     return out, lad.sum(dim=1)
 
 

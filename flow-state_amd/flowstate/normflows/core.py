@@ -233,7 +233,15 @@ class NormalizingFlow(nn.Module):
         "f32" (default: the reference's float32, exact-f32 MFMA products), "bf16x6" or
         "bf16x3" (f32 operands split into bf16 planes on the bf16 matrix cores, DESIGN.md
         'Precision modes').  The spline, base density and everything outside the
-        conditioner GEMMs are unchanged.  Returns self."""
+        conditioner GEMMs are unchanged.
+
+        "f32-general" is the "f32" arithmetic on one runtime-shaped kernel that takes any
+        hidden width up to 512 and any bin count up to 32 (N <= 64): the mode for flows whose
+        (hidden units, bins) pair the library does not instantiate, which the other modes
+        refuse.  It is valid at instantiated shapes too, but those run faster in the default
+        mode (DESIGN.md 'General-shape mode').  In this mode forward_kld / reverse_kld also
+        train at any bin count, layer by layer (autograd_flow.circular_rqs any_k).
+        Returns self."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
         for f in self.flows:

@@ -21,8 +21,11 @@ DEFAULT_MIN_DERIVATIVE = 1e-3  # splines.py:8
 # Conditioner GEMM arithmetic of the fused passes (fs_flow_dims.precision, include/flowstate.h):
 #   "f32"    the reference's float32 products and sums (exact-f32 MFMA), the default;
 #   "bf16x6" f32 operands as three bf16 planes, the six plane products above 2^-24 (f32-level error);
-#   "bf16x3" two planes, three products (16 significant bits per operand).
-PRECISIONS = {"f32": 0, "bf16x6": 1, "bf16x3": 2}
+#   "bf16x3" two planes, three products (16 significant bits per operand);
+#   "f32-general" the "f32" arithmetic on the general-shape kernel: any hidden width <= 512 and
+#            bin count <= 32 (csrc/flow_general_kernels.hip) instead of an instantiated (H, K) pair
+#            (code 4: 3 stays the value the library rejects as unknown).
+PRECISIONS = {"f32": 0, "bf16x6": 1, "bf16x3": 2, "f32-general": 4}
 
 
 def _alternating_mask(features, even):

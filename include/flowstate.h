@@ -44,7 +44,11 @@ typedef struct {
     int32_t precision;   /* conditioner GEMM arithmetic: 0 = f32 MFMA (exact f32 products, the
                           * default); 1 = bf16x6 (f32 operands as 3 bf16 planes, 6 plane
                           * products: f32-level error); 2 = bf16x3 (2 planes, 3 products:
-                          * 16-bit operands).  1 and 2 use their own packed image. */
+                          * 16-bit operands); 4 = f32 MFMA on the general-shape kernel: any
+                          * 1 <= H <= 512, 1 <= K <= 32 (N <= 64) on one runtime-shaped kernel
+                          * instead of an (H, K) instantiation; instantiated shapes are faster
+                          * at precision 0 (3 is not a mode and is rejected).  1, 2 and 4 use their
+                          * own packed image. */
     double tail_bound;
 } fs_flow_dims;
 
@@ -358,6 +362,15 @@ int fs_rqs_forward(int64_t M, int32_t K, int32_t inverse, const float *x, const 
 int fs_rqs_backward(int64_t M, int32_t K, int32_t inverse, const float *x, const float *uw, const float *uh,
                     const float *ud, double tail_bound, const float *g_out, const float *g_lad, float *gx,
                     float *guw, float *guh, float *gud, void *stream);
+
+/* fs_rqs_forward / fs_rqs_backward for any 1 <= K <= 32 (FS_EINVAL otherwise), on
+ * kernels with K a run-time value: the same arguments and the same operations in the same
+ * order (the training spline of flows in the general-shape mode, precision 4). */
+int fs_rqs_forward_any(int64_t M, int32_t K, int32_t inverse, const float *x, const float *uw, const float *uh,
+                       const float *ud, double tail_bound, float *out, float *lad, int32_t *nan_flag, void *stream);
+int fs_rqs_backward_any(int64_t M, int32_t K, int32_t inverse, const float *x, const float *uw, const float *uh,
+                        const float *ud, double tail_bound, const float *g_out, const float *g_lad, float *gx,
+                        float *guw, float *guh, float *gud, void *stream);
 
 /* Conditioner pieces of the training step (ResidualNet in train mode, NF/normflows/
  * nets/resnet.py:7-104; nn.Linear / nn.BatchNorm1d semantics).
