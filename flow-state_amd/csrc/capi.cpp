@@ -821,8 +821,11 @@ int fs_bn_relu_train_bwd(int64_t Bn, int32_t H, const float *x, const float *y, 
 static int check_coupling(const fs_coupling *c, const char *what) {
     REQUIRE(c && c->rows >= 0 && c->D >= 2 && c->D % 2 == 0 && c->hidden >= 1 && c->tail_bound > 0.0,
             "%s: invalid coupling description", what);
-    REQUIRE(c->K == 5 || c->K == 8 || c->K == 15 || c->K == 32, "%s: K=%d not instantiated (5, 8, 15, 32)", what,
-            c->K);
+    if (c->any_k)  // the runtime-K kernels
+        REQUIRE(c->K >= 1 && c->K <= 32, "%s: K=%d outside 1..32 (any_k)", what, c->K);
+    else
+        REQUIRE(c->K == 5 || c->K == 8 || c->K == 15 || c->K == 32, "%s: K=%d not instantiated (5, 8, 15, 32)", what,
+                c->K);
     REQUIRE(c->rows == 0 || (c->identity_features && c->transform_features), "%s: feature indices are NULL", what);
     return FS_OK;
 }
@@ -890,7 +893,8 @@ int fs_coupling_pair_pre(const fs_coupling *s, const float *z, const float *uw, 
                          float *t_density, void *stream) {
     int rc = check_coupling(s, "fs_coupling_pair_pre");
     if (rc || (rc = check_coupling(d, "fs_coupling_pair_pre"))) return rc;
-    REQUIRE(s->K == d->K && s->D == d->D, "fs_coupling_pair_pre: the two layers differ in K or D");
+    REQUIRE(s->K == d->K && s->D == d->D && !s->any_k == !d->any_k,
+            "fs_coupling_pair_pre: the two layers differ in K, any_k or D");
     REQUIRE(s->rows == 0 || (z && uw && uh && ud && t && out && lad_u), "fs_coupling_pair_pre: invalid arguments");
     REQUIRE(z != out, "fs_coupling_pair_pre: out must not alias z");
     REQUIRE(d->rows == 0 || (x && t_density), "fs_coupling_pair_pre: invalid density arguments");
@@ -905,6 +909,9 @@ int fs_coupling_bwd_step(const fs_coupling *f, const float *x_f, const float *g_
     int rc = check_coupling(f, "fs_coupling_bwd_step");
     if (rc || (rc = check_coupling(c, "fs_coupling_bwd_step"))) return rc;
     REQUIRE(f->rows == c->rows && f->D == c->D && c->D <= 256, "fs_coupling_bwd_step: the layers differ in rows or D");
+    // (with any_k = 0 the features layer's K stays unchecked against c's, as it always was)
+    REQUIRE(!f->any_k == !c->any_k && (!c->any_k || f->K == c->K),
+            "fs_coupling_bwd_step: the layers differ in any_k or, with any_k, in K");
     REQUIRE(c->rows == 0 || (x_f && g_t && gx_f && x && params && uw && uh && ud && gx && g_params && g_u),
             "fs_coupling_bwd_step: invalid arguments");
     return hip_rc(fs_coupling_bwd_step_impl(f, x_f, g_t, gx_f, gx_add, c, x, params, uw, uh, ud, g_lq, gx, g_params,
@@ -925,6 +932,9 @@ int fs_coupling_pair_step(const fs_coupling *s, const float *params, const float
     REQUIRE(s->K == d->K && s->D == d->D && s_next->K == s->K && s_next->D == s->D && d_next->D == d->D &&
                 s_next->rows == s->rows && d_next->rows == d->rows && s->D <= 256,
             "fs_coupling_pair_step: the layers differ in K, D or rows (D <= 256)");
+    REQUIRE(!d->any_k == !s->any_k && !s_next->any_k == !s->any_k && !d_next->any_k == !s->any_k &&
+                (!s->any_k || d_next->K == d->K),
+            "fs_coupling_pair_step: the layers differ in any_k or, with any_k, in K");
     REQUIRE(s->rows == 0 || (params && lad_u && out && lq_out && uw_next && uh_next && ud_next && t_next && out_next &&
                              lad_u_next),
             "fs_coupling_pair_step: invalid sampling arguments");
@@ -943,7 +953,8 @@ int fs_coupling_pair_post(const fs_coupling *s, const float *params, const float
                           const float *lq_in_d, float *out_d, float *lq_out_d, void *stream) {
     int rc = check_coupling(s, "fs_coupling_pair_post");
     if (rc || (rc = check_coupling(d, "fs_coupling_pair_post"))) return rc;
-    REQUIRE(s->K == d->K && s->D == d->D, "fs_coupling_pair_post: the two layers differ in K or D");
+    REQUIRE(s->K == d->K && s->D == d->D && !s->any_k == !d->any_k,
+            "fs_coupling_pair_post: the two layers differ in K, any_k or D");
     REQUIRE(s->rows == 0 || (params && lad_u && out && lq_out), "fs_coupling_pair_post: invalid arguments");
     REQUIRE(d->rows == 0 || (x && params_d && uw && uh && ud && out_d && lq_out_d),
             "fs_coupling_pair_post: invalid density arguments");

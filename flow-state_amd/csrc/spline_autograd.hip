@@ -340,16 +340,20 @@ struct KnotsAny {
 
 __device__ __forceinline__ void build_knots_any(int K, const float *u, float B, KnotsAny &kn) {
     float m = u[0];
+#pragma unroll 4
     for (int k = 1; k < K; ++k) m = fmaxf(m, u[k]);
     float s = 0.f;
+#pragma unroll 4
     for (int k = 0; k < K; ++k) {
         kn.p[k] = expf(u[k] - m);
         s += kn.p[k];
     }
+#pragma unroll 4
     for (int k = 0; k < K; ++k) kn.p[k] = kn.p[k] / s;
     const float c1 = 1.f - kMin * (float)K;
     double cs = 0.0;
     kn.c[0] = -B;
+#pragma unroll 4
     for (int k = 0; k < K - 1; ++k) {
         cs += (double)(kMin + c1 * kn.p[k]);
         kn.c[k + 1] = (2.f * B) * (float)cs + (-B);
@@ -359,6 +363,7 @@ __device__ __forceinline__ void build_knots_any(int K, const float *u, float B, 
 
 __device__ __forceinline__ int find_bin_any(int K, float x, const float *knots) {
     int b = -1;
+#pragma unroll 4
     for (int k = 0; k <= K; ++k) {
         const float kv = (k == K) ? knots[K] + 1e-6f : knots[k];
         b += (x >= kv) ? 1 : 0;
@@ -366,13 +371,10 @@ __device__ __forceinline__ int find_bin_any(int K, float x, const float *knots) 
     return b < 0 ? 0 : (b > K - 1 ? K - 1 : b);
 }
 
+// rqs_eval_knots: one element from its built knots; x inside [-B, B]
 template <bool INV>
-__device__ __forceinline__ void rqs_point_any(int K, float xv, const float *uw, const float *uh, const float *dd,
-                                              float B, float &out, float &lad, int32_t *nan_flag) {
-    KnotsAny W, Hh;
-    build_knots_any(K, uw, B, W);
-    build_knots_any(K, uh, B, Hh);
-    const float *wc = W.c, *hc = Hh.c;
+__device__ __forceinline__ void rqs_eval_knots_any(int K, float xv, const float *wc, const float *hc,
+                                                   const float *dd, float &out, float &lad, int32_t *nan_flag) {
     const int b = find_bin_any(K, xv, INV ? hc : wc);
     const float d0 = kMin + softplus(dd[b]), d1 = kMin + softplus(dd[b + 1]);
     const float icw = wc[b], cw1 = wc[b + 1], ich = hc[b], ch1 = hc[b + 1];
@@ -404,6 +406,15 @@ __device__ __forceinline__ void rqs_point_any(int K, float xv, const float *uw, 
 }
 
 template <bool INV>
+__device__ __forceinline__ void rqs_point_any(int K, float xv, const float *uw, const float *uh, const float *dd,
+                                              float B, float &out, float &lad, int32_t *nan_flag) {
+    KnotsAny W, Hh;
+    build_knots_any(K, uw, B, W);
+    build_knots_any(K, uh, B, Hh);
+    rqs_eval_knots_any<INV>(K, xv, W.c, Hh.c, dd, out, lad, nan_flag);
+}
+
+template <bool INV>
 __global__ __launch_bounds__(256) void rqs_forward_any_kernel(int64_t M, int K, const float *__restrict__ x,
                                                               const float *__restrict__ uw,
                                                               const float *__restrict__ uh,
@@ -428,44 +439,31 @@ __device__ __forceinline__ void knots_backward_any(int K, const KnotsAny &kn, in
     const float c1 = 1.f - kMin * (float)K;
     float gw[kAnyMaxK];
     float suffix = 0.f;
+#pragma unroll 4
     for (int j = K - 1; j >= 0; --j) {
         gw[j] = suffix;
         const float gcj = (j == b) ? g_b : ((j == b + 1) ? g_b1 : 0.f);
         if (j >= 1) suffix += (2.f * B) * gcj;
     }
     float dot = 0.f;
+#pragma unroll 4
     for (int j = 0; j < K; ++j) dot += kn.p[j] * (c1 * gw[j]);
+#pragma unroll 4
     for (int j = 0; j < K; ++j) gu[j] = kn.p[j] * (c1 * gw[j] - dot);
 }
 
+// rqs_bwd_core with the knot adjoints left sparse: only knots b and b + 1 of the element's
+// bin carry one (gw0 / gw1 of the width knots, gh0 / gh1 of the height knots)
+struct BinAdjoint {
+    int b;
+    float gw0, gw1, gh0, gh1;
+};
+
+// the adjoint core of one element inside [-B, B] from its built knots: gx, the bin's knot
+// adjoints and the derivative logits' adjoints gud[0..K]
 template <bool INV>
-__global__ __launch_bounds__(256) void rqs_backward_any_kernel(int64_t M, int K, const float *__restrict__ x,
-                                                               const float *__restrict__ uw,
-                                                               const float *__restrict__ uh,
-                                                               const float *__restrict__ ud, float B,
-                                                               const float *__restrict__ g_out,
-                                                               const float *__restrict__ g_lad,
-                                                               float *__restrict__ gx, float *__restrict__ guw,
-                                                               float *__restrict__ guh, float *__restrict__ gud) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    const float xv = x[i];
-    const float go = g_out ? g_out[i] : 0.f, gl = g_lad ? g_lad[i] : 0.f;
-    float *pw = guw + i * K, *ph = guh + i * K, *pd = gud + i * (K + 1);
-    if (!(xv >= -B && xv <= B)) {
-        gx[i] = go;
-        for (int k = 0; k < K; ++k) {
-            pw[k] = 0.f;
-            ph[k] = 0.f;
-        }
-        for (int k = 0; k <= K; ++k) pd[k] = 0.f;
-        return;
-    }
-    KnotsAny W, Hh;
-    build_knots_any(K, uw + i * K, B, W);
-    build_knots_any(K, uh + i * K, B, Hh);
-    const float *wc = W.c, *hc = Hh.c, *dd = ud + i * (K + 1);
-    // rqs_bwd_core
+__device__ __forceinline__ BinAdjoint rqs_bwd_core_any(int K, float xv, const float *wc, const float *hc,
+                                                       const float *dd, float go, float gl, float &gx, float *gud) {
     const int b = find_bin_any(K, xv, INV ? hc : wc);
     const float e0 = dd[b], e1 = dd[b + 1];
     const float d0 = kMin + softplus(e0), d1 = kMin + softplus(e1);
@@ -545,15 +543,53 @@ __global__ __launch_bounds__(256) void rqs_backward_any_kernel(int64_t M, int K,
     }
     g_ih += g_s / ibw;
     g_ibw -= g_s * s / ibw;
-    gx[i] = g_x;
+    gx = g_x;
     for (int k = 0; k <= K; ++k) {
         float g = 0.f;
         if (k == b) g = g_d0 * softplus_grad(e0);
         if (k == b + 1) g = g_d1 * softplus_grad(e1);
-        pd[k] = g;
+        gud[k] = g;
     }
-    knots_backward_any(K, W, b, g_icw - g_ibw, g_ibw, B, pw);
-    knots_backward_any(K, Hh, b, g_ich - g_ih, g_ih, B, ph);
+    return BinAdjoint{b, g_icw - g_ibw, g_ibw, g_ich - g_ih, g_ih};
+}
+
+// adjoints of one element inside [-B, B]: gx, guw[K], guh[K], gud[K+1]
+template <bool INV>
+__device__ __forceinline__ void rqs_point_bwd_any(int K, float xv, const float *uw, const float *uh, const float *dd,
+                                                  float B, float go, float gl, float &gx, float *guw, float *guh,
+                                                  float *gud) {
+    KnotsAny W, Hh;
+    build_knots_any(K, uw, B, W);
+    build_knots_any(K, uh, B, Hh);
+    const BinAdjoint a = rqs_bwd_core_any<INV>(K, xv, W.c, Hh.c, dd, go, gl, gx, gud);
+    knots_backward_any(K, W, a.b, a.gw0, a.gw1, B, guw);
+    knots_backward_any(K, Hh, a.b, a.gh0, a.gh1, B, guh);
+}
+
+template <bool INV>
+__global__ __launch_bounds__(256) void rqs_backward_any_kernel(int64_t M, int K, const float *__restrict__ x,
+                                                               const float *__restrict__ uw,
+                                                               const float *__restrict__ uh,
+                                                               const float *__restrict__ ud, float B,
+                                                               const float *__restrict__ g_out,
+                                                               const float *__restrict__ g_lad,
+                                                               float *__restrict__ gx, float *__restrict__ guw,
+                                                               float *__restrict__ guh, float *__restrict__ gud) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    const float xv = x[i];
+    const float go = g_out ? g_out[i] : 0.f, gl = g_lad ? g_lad[i] : 0.f;
+    float *pw = guw + i * K, *ph = guh + i * K, *pd = gud + i * (K + 1);
+    if (!(xv >= -B && xv <= B)) {
+        gx[i] = go;
+        for (int k = 0; k < K; ++k) {
+            pw[k] = 0.f;
+            ph[k] = 0.f;
+        }
+        for (int k = 0; k <= K; ++k) pd[k] = 0.f;
+        return;
+    }
+    rqs_point_bwd_any<INV>(K, xv, uw + i * K, uh + i * K, ud + i * (K + 1), B, go, gl, gx[i], pw, ph, pd);
 }
 
 
@@ -1226,6 +1262,473 @@ __global__ __launch_bounds__(256) void coupling_bwd_step4_kernel(CouplingArgs cf
     density_bwd_row4<K>(c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, kx);
 }
 
+// ---------------------------------------------------------------------------
+// Every coupling kernel above with K a run-time value, 1 <= K <= kAnyMaxK (fs_coupling.any_k:
+// the general-shape mode's training step at a bin count no kernel is instantiated for).
+// Separate copies rather than a K policy on the row functions above: the spline underneath
+// differs (rqs_point_any and its adjoint index per-thread arrays of kAnyMaxK in private
+// memory and keep the knot adjoints sparse, where the instantiated ones scan registers),
+// and the instantiated kernels stay the code they were.  Same layout (one wave per row,
+// lane = feature, the two- / four-wave variants of coupling_waves(), D <= kCplMaxD in the
+// step kernels), same operations in the same order, so each row is what the single-layer
+// entry points give, and at K in {5, 8, 15, 32} what the instantiated kernels give up to the
+// compiler's choice of instructions.
+__device__ __forceinline__ void cond_params_any(int K, const float *p, float sq, float *w, float *h) {
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+        w[k] = p[k] / sq;
+        h[k] = p[K + k] / sq;
+    }
+}
+
+__device__ __forceinline__ void density_fwd_row_any(int K, const CouplingArgs &c, const DensityFwdArgs &d, int64_t row,
+                                                    float *rb = nullptr) {
+    const int lane = threadIdx.x & 63;
+    const float *xr = d.x + row * c.D;
+    float sc = 0.f, su = 0.f;
+    for (int j = lane; j < c.n; j += 64) {
+        const int pi = (int)c.id[j], pt = (int)c.tr[j];
+        const float xi = xr[pi], xt = xr[pt];
+        float yt = xt, lt = 0.f;
+        if (xt >= -c.bound && xt <= c.bound) {
+            const float *p = d.params + (row * c.n + j) * (3 * K + 1);
+            float w[kAnyMaxK], h[kAnyMaxK];
+            cond_params_any(K, p, c.sq, w, h);
+            rqs_point_any<false>(K, xt, w, h, p + 2 * K, c.bound, yt, lt, nullptr);
+        }
+        float yi = xi, li = 0.f;
+        if (xi >= -c.bound && xi <= c.bound)
+            rqs_point_any<false>(K, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
+        d.out[row * c.D + (pt + c.D - c.split) % c.D] = yt;
+        d.out[row * c.D + (pi + c.D - c.split) % c.D] = yi;
+        if (rb) {
+            rb[(pt + c.D - c.split) % c.D] = yt;
+            rb[(pi + c.D - c.split) % c.D] = yi;
+        }
+        sc += lt;
+        su += li;
+    }
+    sc = wave_sum(sc);
+    su = wave_sum(su);
+    if (lane == 0) d.lq_out[row] = (d.lq_in ? d.lq_in[row] : 0.f) + (sc + su);
+}
+
+__global__ __launch_bounds__(256) void coupling_density_fwd_any_kernel(int K, CouplingArgs c, DensityFwdArgs d) {
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    if (row < c.rows) density_fwd_row_any(K, c, d, row);
+}
+
+// density_bwd_row; the adjoints that need no rescaling go straight to their rows of g_params / g_u
+__device__ __forceinline__ void density_bwd_row_any(int K, const CouplingArgs &c, const float *__restrict__ x,
+                                                    const float *__restrict__ params, const float *__restrict__ uw,
+                                                    const float *__restrict__ uh, const float *__restrict__ ud,
+                                                    const float *gor, const float *__restrict__ g_lq, float *gx,
+                                                    float *g_params, float *g_u, int64_t row, int part) {
+    const int lane = threadIdx.x & 63;
+    const float *xr = x + row * c.D;
+    const float gl = g_lq ? g_lq[row] : 0.f;
+    const int P = 3 * K + 1;
+    for (int j = lane; j < c.n; j += 64) {
+        const int pi = (int)c.id[j], pt = (int)c.tr[j];
+        const float xi = xr[pi], xt = xr[pt];
+        const float got = gor ? gor[(pt + c.D - c.split) % c.D] : 0.f;
+        const float goi = gor ? gor[(pi + c.D - c.split) % c.D] : 0.f;
+        float *gp = g_params + (row * c.n + j) * P;
+        // g_u row: [uw n*K | uh n*K | ud n*(K+1)], the parameters' own layouts back to back
+        float *guw = g_u + row * c.n * P + j * K;
+        float *guh = guw + c.n * K;
+        float *gud = g_u + row * c.n * P + 2 * c.n * K + j * (K + 1);
+        if (part == 1) {
+        } else if (xt >= -c.bound && xt <= c.bound) {
+            const float *p = params + (row * c.n + j) * P;
+            float w[kAnyMaxK], h[kAnyMaxK], gw[kAnyMaxK], gh[kAnyMaxK];
+            cond_params_any(K, p, c.sq, w, h);
+            float g;
+            rqs_point_bwd_any<false>(K, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, gp + 2 * K);
+            gx[row * c.D + pt] = g;
+            for (int k = 0; k < K; ++k) {
+                gp[k] = gw[k] / c.sq;
+                gp[K + k] = gh[k] / c.sq;
+            }
+        } else {
+            gx[row * c.D + pt] = got;
+            for (int k = 0; k < P; ++k) gp[k] = 0.f;
+        }
+        if (part == 0) {
+        } else if (xi >= -c.bound && xi <= c.bound) {
+            float g;
+            rqs_point_bwd_any<false>(K, xi, uw + j * K, uh + j * K, ud + j * (K + 1), c.bound, goi, gl, g, guw, guh,
+                                     gud);
+            gx[row * c.D + pi] = g;
+        } else {
+            gx[row * c.D + pi] = goi;
+            for (int k = 0; k < K; ++k) {
+                guw[k] = 0.f;
+                guh[k] = 0.f;
+            }
+            for (int k = 0; k <= K; ++k) gud[k] = 0.f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void coupling_density_bwd_any_kernel(
+    int K, CouplingArgs c, const float *__restrict__ x, const float *__restrict__ params,
+    const float *__restrict__ uw, const float *__restrict__ uh, const float *__restrict__ ud,
+    const float *__restrict__ g_out, const float *__restrict__ g_lq, float *gx, float *g_params, float *g_u) {
+    const int wv = threadIdx.x >> 6;
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (wv >> 1);
+    if (row >= c.rows) return;
+    density_bwd_row_any(K, c, x, params, uw, uh, ud, g_out ? g_out + row * c.D : nullptr, g_lq, gx, g_params, g_u,
+                        row, wv & 1);
+}
+
+__global__ __launch_bounds__(256) void coupling_bwd_step_any_kernel(
+    int K, CouplingArgs cf, const float *__restrict__ xf, const float *__restrict__ g_t, float *gxf,
+    const float *__restrict__ gx_add, CouplingArgs c, const float *__restrict__ x, const float *__restrict__ params,
+    const float *__restrict__ uw, const float *__restrict__ uh, const float *__restrict__ ud,
+    const float *__restrict__ g_lq, float *gx, float *g_params, float *g_u) {
+    __shared__ float rbuf[kCplRows][kCplMaxDB];
+    const int wv = threadIdx.x >> 6;
+    float *rb = rbuf[wv >> 1];
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (wv >> 1);
+    const bool live = row < c.rows;
+    if (live && (wv & 1) == 0) features_bwd_row(cf, xf, g_t, gxf, gx_add, row, rb);
+    __syncthreads();
+    if (!live) return;
+    density_bwd_row_any(K, c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, wv & 1);
+}
+
+__device__ __forceinline__ void sample_pre_row_any(int K, const CouplingArgs &c, const SamplePreArgs &s, int64_t row,
+                                                   const float *zr = nullptr) {
+    const int lane = threadIdx.x & 63;
+    if (!zr) zr = s.z + row * c.D;
+    float su = 0.f;
+    for (int j = lane; j < c.n; j += 64) {
+        const int pi = (int)c.id[j], pt = (int)c.tr[j];
+        const float xi = zr[(pi + c.split) % c.D];
+        float yi = xi, li = 0.f;
+        if (xi >= -c.bound && xi <= c.bound)
+            rqs_point_any<true>(K, xi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, yi, li, s.nan_flag);
+        const float v = c.scale * yi;
+        s.t[row * 2 * c.n + j] = cosf(v);
+        s.t[row * 2 * c.n + c.n + j] = sinf(v);
+        s.out[row * c.D + pi] = yi;
+        s.out[row * c.D + pt] = zr[(pt + c.split) % c.D];
+        su += li;
+    }
+    su = wave_sum(su);
+    if (lane == 0) s.lad_u[row] = su;
+}
+
+__global__ __launch_bounds__(256) void coupling_sample_pre_any_kernel(int K, CouplingArgs c, SamplePreArgs s) {
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    if (row < c.rows) sample_pre_row_any(K, c, s, row);
+}
+
+__device__ __forceinline__ void sample_post_row_any(int K, const CouplingArgs &c, const SamplePostArgs &s, int64_t row,
+                                                    float *rb = nullptr) {
+    const int lane = threadIdx.x & 63;
+    float sc = 0.f;
+    for (int j = lane; j < c.n; j += 64) {
+        const int pt = (int)c.tr[j];
+        if (rb) {
+            const int pi = (int)c.id[j];
+            rb[pi] = s.out[row * c.D + pi];  // written by this layer's pre launch
+        }
+        const float xt = s.out[row * c.D + pt];
+        float yt = xt, lt = 0.f;
+        if (xt >= -c.bound && xt <= c.bound) {
+            const float *p = s.params + (row * c.n + j) * (3 * K + 1);
+            float w[kAnyMaxK], h[kAnyMaxK];
+            cond_params_any(K, p, c.sq, w, h);
+            rqs_point_any<true>(K, xt, w, h, p + 2 * K, c.bound, yt, lt, s.nan_flag);
+        }
+        s.out[row * c.D + pt] = yt;
+        if (rb) rb[pt] = yt;
+        sc += lt;
+    }
+    sc = wave_sum(sc);
+    if (lane == 0) s.lq_out[row] = (s.lq_in ? s.lq_in[row] : 0.f) - (s.lad_u[row] + sc);
+}
+
+__global__ __launch_bounds__(256) void coupling_sample_post_any_kernel(int K, CouplingArgs c, SamplePostArgs s) {
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    if (row < c.rows) sample_post_row_any(K, c, s, row);
+}
+
+__global__ __launch_bounds__(256) void coupling_pair_pre_any_kernel(int K, CouplingArgs cs, SamplePreArgs s,
+                                                                    CouplingArgs cd, const float *__restrict__ x,
+                                                                    float *t, unsigned nb0) {
+    const bool dens = blockIdx.x >= nb0;
+    const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x) * kCplRows + (threadIdx.x >> 6);
+    if (!dens) {
+        if (row < cs.rows) sample_pre_row_any(K, cs, s, row);
+    } else if (row < cd.rows) {
+        features_row(cd, x, t, row);
+    }
+}
+
+__global__ __launch_bounds__(256) void coupling_pair_post_any_kernel(int K, CouplingArgs cs, SamplePostArgs s,
+                                                                     CouplingArgs cd, DensityFwdArgs d, unsigned nb0) {
+    const bool dens = blockIdx.x >= nb0;
+    const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x) * kCplRows + (threadIdx.x >> 6);
+    if (!dens) {
+        if (row < cs.rows) sample_post_row_any(K, cs, s, row);
+    } else if (row < cd.rows) {
+        density_fwd_row_any(K, cd, d, row);
+    }
+}
+
+__global__ __launch_bounds__(256) void coupling_pair_step_any_kernel(int K, CouplingArgs cs, SamplePostArgs s,
+                                                                     CouplingArgs cs2, SamplePreArgs s2,
+                                                                     CouplingArgs cd, DensityFwdArgs d,
+                                                                     CouplingArgs cd2, float *t_d2, unsigned nb0) {
+    __shared__ float rbuf[kCplRows][kCplMaxD];
+    float *rb = rbuf[threadIdx.x >> 6];
+    const bool dens = blockIdx.x >= nb0;
+    const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x) * kCplRows + (threadIdx.x >> 6);
+    const bool live = dens ? row < cd.rows : row < cs.rows;
+    if (live) {
+        if (!dens)
+            sample_post_row_any(K, cs, s, row, rb);
+        else
+            density_fwd_row_any(K, cd, d, row, rb);
+    }
+    __syncthreads();  // the row's LDS copy, written by every lane of its wave
+    if (!live) return;
+    if (!dens)
+        sample_pre_row_any(K, cs2, s2, row, rb);
+    else
+        features_row(cd2, d.out, t_d2, row, rb);
+}
+
+// knots_pair: this wave's knot set (own) into slot w of kx (kAnyMaxK + 1 knots of 64 lanes per
+// slot are reserved, K + 1 are used) and, with its partner's (slot w ^ 1), back as (width,
+// height) knots
+__device__ __forceinline__ void knots_pair_any(int K, float *kx, int w, int h, const float *own, float *wc,
+                                               float *hc) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll 4
+    for (int k = 0; k <= K; ++k) kx[(w * (K + 1) + k) * 64 + lane] = own[k];
+    __syncthreads();
+#pragma unroll 4
+    for (int k = 0; k <= K; ++k) {
+        const float oc = kx[((w ^ 1) * (K + 1) + k) * 64 + lane];
+        wc[k] = h == 0 ? own[k] : oc;
+        hc[k] = h == 0 ? oc : own[k];
+    }
+}
+
+__device__ __forceinline__ void sample_post_row2_any(int K, const CouplingArgs &c, const SamplePostArgs &s, int64_t row,
+                                                     float *rb, float *kx, int h) {
+    const int lane = threadIdx.x & 63;
+    float sc = 0.f;
+    for (int j0 = 0; j0 < c.n; j0 += 64) {  // uniform trip count: the pair meets at its barriers
+        const int j = j0 + lane;
+        const bool on = j < c.n;
+        const int jj = on ? j : 0;
+        const int pt = (int)c.tr[jj];
+        if (h == 0 && on) {
+            const int pi = (int)c.id[jj];
+            rb[pi] = s.out[row * c.D + pi];  // written by this layer's pre launch
+        }
+        const float xt = s.out[row * c.D + pt];
+        const float *p = s.params + (row * c.n + jj) * (3 * K + 1);
+        KnotsAny kn;
+        {
+            float u[kAnyMaxK];
+            for (int k = 0; k < K; ++k) u[k] = p[h * K + k] / c.sq;  // cond_params' half
+            build_knots_any(K, u, c.bound, kn);
+        }
+        float wc[kAnyMaxK + 1], hc[kAnyMaxK + 1];
+        knots_pair_any(K, kx, h, h, kn.c, wc, hc);
+        float yt = xt, lt = 0.f;
+        if (on && xt >= -c.bound && xt <= c.bound)
+            rqs_eval_knots_any<true>(K, xt, wc, hc, p + 2 * K, yt, lt, h == 0 ? s.nan_flag : nullptr);
+        if (h == 0 && on) {
+            s.out[row * c.D + pt] = yt;
+            rb[pt] = yt;
+        }
+        sc += on ? lt : 0.f;
+        __syncthreads();  // the partner has read this round's knots
+    }
+    sc = wave_sum(sc);
+    if (h == 0 && lane == 0) s.lq_out[row] = (s.lq_in ? s.lq_in[row] : 0.f) - (s.lad_u[row] + sc);
+}
+
+__device__ __forceinline__ void sample_pre_row2_any(int K, const CouplingArgs &c, const SamplePreArgs &s, int64_t row,
+                                                    const float *zr, float *kx, int h) {
+    const int lane = threadIdx.x & 63;
+    float su = 0.f;
+    for (int j0 = 0; j0 < c.n; j0 += 64) {
+        const int j = j0 + lane;
+        const bool on = j < c.n;
+        const int jj = on ? j : 0;
+        const int pi = (int)c.id[jj], pt = (int)c.tr[jj];
+        const float xi = zr[(pi + c.split) % c.D];
+        KnotsAny kn;
+        build_knots_any(K, (h == 0 ? s.uw : s.uh) + jj * K, c.bound, kn);
+        float wc[kAnyMaxK + 1], hc[kAnyMaxK + 1];
+        knots_pair_any(K, kx, h, h, kn.c, wc, hc);
+        float yi = xi, li = 0.f;
+        if (on && xi >= -c.bound && xi <= c.bound)
+            rqs_eval_knots_any<true>(K, xi, wc, hc, s.ud + jj * (K + 1), yi, li, h == 0 ? s.nan_flag : nullptr);
+        const float v = c.scale * yi;
+        if (on) {
+            if (h == 0) {
+                s.t[row * 2 * c.n + j] = cosf(v);
+                s.out[row * c.D + pi] = yi;
+                s.out[row * c.D + pt] = zr[(pt + c.split) % c.D];
+            } else {
+                s.t[row * 2 * c.n + c.n + j] = sinf(v);
+            }
+        }
+        su += on ? li : 0.f;
+        __syncthreads();
+    }
+    su = wave_sum(su);
+    if (h == 0 && lane == 0) s.lad_u[row] = su;
+}
+
+__device__ __forceinline__ float density_fwd_row2_any(int K, const CouplingArgs &c, const DensityFwdArgs &d,
+                                                      int64_t row, float *rb, float *red, int h) {
+    const int lane = threadIdx.x & 63;
+    const float *xr = d.x + row * c.D;
+    float sl = 0.f;
+    for (int j = lane; j < c.n; j += 64) {
+        if (h == 0) {
+            const int pt = (int)c.tr[j];
+            const float xt = xr[pt];
+            float yt = xt, lt = 0.f;
+            if (xt >= -c.bound && xt <= c.bound) {
+                const float *p = d.params + (row * c.n + j) * (3 * K + 1);
+                float w[kAnyMaxK], hh[kAnyMaxK];
+                cond_params_any(K, p, c.sq, w, hh);
+                rqs_point_any<false>(K, xt, w, hh, p + 2 * K, c.bound, yt, lt, nullptr);
+            }
+            d.out[row * c.D + (pt + c.D - c.split) % c.D] = yt;
+            rb[(pt + c.D - c.split) % c.D] = yt;
+            sl += lt;
+        } else {
+            const int pi = (int)c.id[j];
+            const float xi = xr[pi];
+            float yi = xi, li = 0.f;
+            if (xi >= -c.bound && xi <= c.bound)
+                rqs_point_any<false>(K, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
+            d.out[row * c.D + (pi + c.D - c.split) % c.D] = yi;
+            rb[(pi + c.D - c.split) % c.D] = yi;
+            sl += li;
+        }
+    }
+    sl = wave_sum(sl);
+    if (h == 1 && lane == 0) red[0] = sl;
+    return sl;
+}
+
+__global__ __launch_bounds__(128) void coupling_pair_step2_any_kernel(int K, CouplingArgs cs, SamplePostArgs s,
+                                                                      CouplingArgs cs2, SamplePreArgs s2,
+                                                                      CouplingArgs cd, DensityFwdArgs d,
+                                                                      CouplingArgs cd2, float *t_d2, unsigned nb0) {
+    __shared__ float rb[kCplMaxD];
+    __shared__ float kx[2 * (kAnyMaxK + 1) * 64];
+    __shared__ float red[1];
+    const int h = (int)(threadIdx.x >> 6);
+    const bool dens = blockIdx.x >= nb0;
+    const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x);
+    if (!dens) {
+        if (row >= cs.rows) return;  // whole workgroup: no barrier is left waiting
+        sample_post_row2_any(K, cs, s, row, rb, kx, h);
+        __syncthreads();  // the row in LDS
+        sample_pre_row2_any(K, cs2, s2, row, rb, kx, h);
+        return;
+    }
+    if (row >= cd.rows) return;
+    const float sl = density_fwd_row2_any(K, cd, d, row, rb, red, h);
+    __syncthreads();  // the row in LDS, the unconditional log-det sum in red
+    const int lane = threadIdx.x & 63;
+    if (h == 0 && lane == 0) d.lq_out[row] = (d.lq_in ? d.lq_in[row] : 0.f) + (sl + red[0]);  // density_fwd_row's order
+    for (int j = lane; j < cd2.n; j += 64) {  // features_row, cosines on wave 0, sines on wave 1
+        const float v = cd2.scale * rb[cd2.id[j]];
+        if (h == 0)
+            t_d2[row * 2 * cd2.n + j] = cosf(v);
+        else
+            t_d2[row * 2 * cd2.n + cd2.n + j] = sinf(v);
+    }
+}
+
+__device__ __forceinline__ void density_bwd_row4_any(int K, const CouplingArgs &c, const float *__restrict__ x,
+                                                     const float *__restrict__ params, const float *__restrict__ uw,
+                                                     const float *__restrict__ uh, const float *__restrict__ ud,
+                                                     const float *gor, const float *__restrict__ g_lq, float *gx,
+                                                     float *g_params, float *g_u, int64_t row, float *kx) {
+    const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6), part = wv >> 1, h = wv & 1;
+    const float *xr = x + row * c.D;
+    const float gl = g_lq ? g_lq[row] : 0.f;
+    const int P = 3 * K + 1;
+    for (int j0 = 0; j0 < c.n; j0 += 64) {
+        const int j = j0 + lane;
+        const bool on = j < c.n;
+        const int jj = on ? j : 0;
+        const int pi = (int)c.id[jj], pt = (int)c.tr[jj];
+        const int pos = part == 0 ? pt : pi;
+        const float xv = xr[pos];
+        const float go = gor ? gor[(pos + c.D - c.split) % c.D] : 0.f;
+        const float *p = params + (row * c.n + jj) * P;
+        KnotsAny kn;
+        if (part == 0) {
+            float u[kAnyMaxK];
+            for (int k = 0; k < K; ++k) u[k] = p[h * K + k] / c.sq;  // cond_params' half
+            build_knots_any(K, u, c.bound, kn);
+        } else {
+            build_knots_any(K, (h == 0 ? uw : uh) + jj * K, c.bound, kn);
+        }
+        float wc[kAnyMaxK + 1], hc[kAnyMaxK + 1];
+        knots_pair_any(K, kx, wv, h, kn.c, wc, hc);
+        const bool inside = xv >= -c.bound && xv <= c.bound;
+        float *gp = g_params + (row * c.n + jj) * P;
+        // g_u row: [uw n*K | uh n*K | ud n*(K+1)], the parameters' own layouts back to back
+        float *guw = g_u + row * c.n * P + jj * K;
+        float *guh = guw + c.n * K;
+        float *gud = g_u + row * c.n * P + 2 * c.n * K + jj * (K + 1);
+        // what this wave stores: its knot set's parameter adjoints and, on h == 0, gx and the
+        // derivative logits' adjoints
+        float *gk_out = part == 0 ? gp + h * K : (h == 0 ? guw : guh);
+        float *gd_out = part == 0 ? gp + 2 * K : gud;
+        if (on && inside) {
+            float g, gd[kAnyMaxK + 1], gk[kAnyMaxK];
+            const BinAdjoint a = rqs_bwd_core_any<false>(K, xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1), go,
+                                                         gl, g, gd);
+            knots_backward_any(K, kn, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
+            for (int k = 0; k < K; ++k) gk_out[k] = part == 0 ? gk[k] / c.sq : gk[k];
+            if (h == 0) {
+                gx[row * c.D + pos] = g;
+                for (int k = 0; k <= K; ++k) gd_out[k] = gd[k];
+            }
+        } else if (on) {
+            for (int k = 0; k < K; ++k) gk_out[k] = 0.f;
+            if (h == 0) {
+                gx[row * c.D + pos] = go;
+                for (int k = 0; k <= K; ++k) gd_out[k] = 0.f;
+            }
+        }
+        __syncthreads();  // the partners have read this round's knots
+    }
+}
+
+__global__ __launch_bounds__(256) void coupling_bwd_step4_any_kernel(
+    int K, CouplingArgs cf, const float *__restrict__ xf, const float *__restrict__ g_t, float *gxf,
+    const float *__restrict__ gx_add, CouplingArgs c, const float *__restrict__ x, const float *__restrict__ params,
+    const float *__restrict__ uw, const float *__restrict__ uh, const float *__restrict__ ud,
+    const float *__restrict__ g_lq, float *gx, float *g_params, float *g_u) {
+    __shared__ float rb[kCplMaxDB];
+    __shared__ float kx[4 * (kAnyMaxK + 1) * 64];
+    const int64_t row = blockIdx.x;
+    if (row >= c.rows) return;  // whole workgroup
+    if (threadIdx.x < 64) features_bwd_row(cf, xf, g_t, gxf, gx_add, row, rb);
+    __syncthreads();
+    density_bwd_row4_any(K, c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, kx);
+}
+
 }  // namespace fs
 
 using namespace fs;
@@ -1336,15 +1839,23 @@ static fs::CouplingArgs coupling_args(const fs_coupling *c) {
     return a;
 }
 
+// any_k descriptors: K in the runtime-K kernels' range (capi.cpp checks it with a message)
+static bool any_k_ok(const fs_coupling *c) { return c->K >= 1 && c->K <= kAnyMaxK; }
+
 #define FS_COUPLING_LAUNCH(KERNEL, ...)                                                         \
     const fs::CouplingArgs a = coupling_args(cp);                                               \
+    if (cp->any_k && !any_k_ok(cp)) return hipErrorInvalidValue;                                \
     if (a.rows <= 0) return hipSuccess;                                                         \
     const dim3 grid((unsigned)((a.rows + kCplRows - 1) / kCplRows)), block(64 * kCplRows);                                  \
+    if (cp->any_k) {                                                                            \
+        hipLaunchKernelGGL(KERNEL##_any_kernel, grid, block, 0, st, (int)cp->K, a, __VA_ARGS__); \
+        return hipGetLastError();                                                               \
+    }                                                                                           \
     switch (cp->K) {                                                                            \
-    case 5: hipLaunchKernelGGL((KERNEL<5>), grid, block, 0, st, a, __VA_ARGS__); break;         \
-    case 8: hipLaunchKernelGGL((KERNEL<8>), grid, block, 0, st, a, __VA_ARGS__); break;         \
-    case 15: hipLaunchKernelGGL((KERNEL<15>), grid, block, 0, st, a, __VA_ARGS__); break;       \
-    case 32: hipLaunchKernelGGL((KERNEL<32>), grid, block, 0, st, a, __VA_ARGS__); break;       \
+    case 5: hipLaunchKernelGGL((KERNEL##_kernel<5>), grid, block, 0, st, a, __VA_ARGS__); break;   \
+    case 8: hipLaunchKernelGGL((KERNEL##_kernel<8>), grid, block, 0, st, a, __VA_ARGS__); break;   \
+    case 15: hipLaunchKernelGGL((KERNEL##_kernel<15>), grid, block, 0, st, a, __VA_ARGS__); break; \
+    case 32: hipLaunchKernelGGL((KERNEL##_kernel<32>), grid, block, 0, st, a, __VA_ARGS__); break; \
     default: return hipErrorInvalidValue;                                                       \
     }                                                                                           \
     return hipGetLastError();
@@ -1353,7 +1864,7 @@ hipError_t fs_coupling_density_fwd_impl(const fs_coupling *cp, const float *x, c
                                         const float *uh, const float *ud, const float *lq_in, float *out, float *lq_out,
                                         hipStream_t st) {
     const DensityFwdArgs d{x, params, uw, uh, ud, lq_in, out, lq_out};
-    FS_COUPLING_LAUNCH(coupling_density_fwd_kernel, d)
+    FS_COUPLING_LAUNCH(coupling_density_fwd, d)
 }
 
 hipError_t fs_coupling_density_bwd_impl(const fs_coupling *cp, const float *x, const float *params, const float *uw,
@@ -1363,6 +1874,12 @@ hipError_t fs_coupling_density_bwd_impl(const fs_coupling *cp, const float *x, c
     const fs::CouplingArgs a = coupling_args(cp);
     if (a.rows <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((a.rows + kCplRows - 1) / kCplRows);
+    if (cp->any_k) {
+        if (!any_k_ok(cp)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(coupling_density_bwd_any_kernel, dim3(grid), dim3(128 * kCplRows), 0, st, (int)cp->K, a, x,
+                           params, uw, uh, ud, g_out, g_lq, gx, g_params, g_u);
+        return hipGetLastError();
+    }
 #define FS_DB(KK)                                                                                                  \
     if (cp->K == KK) {                                                                                             \
         hipLaunchKernelGGL(coupling_density_bwd_kernel<KK>, dim3(grid), dim3(128 * kCplRows), 0, st, a, x, params, uw, \
@@ -1383,6 +1900,16 @@ hipError_t fs_coupling_bwd_step_impl(const fs_coupling *fp, const float *xf, con
     if (a.rows <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((a.rows + kCplRows - 1) / kCplRows);
     const bool four = coupling_waves() && a.rows <= 0x7fffffff;
+    if (cp->any_k) {
+        if (!any_k_ok(cp)) return hipErrorInvalidValue;
+        if (four)
+            hipLaunchKernelGGL(coupling_bwd_step4_any_kernel, dim3((unsigned)a.rows), dim3(256), 0, st, (int)cp->K, af,
+                               xf, g_t, gxf, gx_add, a, x, params, uw, uh, ud, g_lq, gx, g_params, g_u);
+        else
+            hipLaunchKernelGGL(coupling_bwd_step_any_kernel, dim3(grid), dim3(128 * kCplRows), 0, st, (int)cp->K, af,
+                               xf, g_t, gxf, gx_add, a, x, params, uw, uh, ud, g_lq, gx, g_params, g_u);
+        return hipGetLastError();
+    }
 #define FS_DB(KK)                                                                                                  \
     if (cp->K == KK) {                                                                                             \
         if (four)                                                                                                  \
@@ -1402,29 +1929,34 @@ hipError_t fs_coupling_sample_pre_impl(const fs_coupling *cp, const float *z, co
                                        const float *ud, float *t, float *out, float *lad_u, int32_t *nan_flag,
                                        hipStream_t st) {
     const SamplePreArgs s{z, uw, uh, ud, t, out, lad_u, nan_flag};
-    FS_COUPLING_LAUNCH(coupling_sample_pre_kernel, s)
+    FS_COUPLING_LAUNCH(coupling_sample_pre, s)
 }
 
 hipError_t fs_coupling_sample_post_impl(const fs_coupling *cp, const float *params, const float *lad_u,
                                         const float *lq_in, float *out, float *lq_out, int32_t *nan_flag,
                                         hipStream_t st) {
     const SamplePostArgs s{params, lad_u, lq_in, out, lq_out, nan_flag};
-    FS_COUPLING_LAUNCH(coupling_sample_post_kernel, s)
+    FS_COUPLING_LAUNCH(coupling_sample_post, s)
 }
 #undef FS_COUPLING_LAUNCH
 
 #define FS_PAIR_LAUNCH(KERNEL, ...)                                                                     \
     const fs::CouplingArgs as = coupling_args(sp), ad = coupling_args(dp);                              \
-    if (sp->K != dp->K || as.rows < 0 || ad.rows < 0) return hipErrorInvalidValue;                     \
+    if (sp->K != dp->K || !sp->any_k != !dp->any_k || as.rows < 0 || ad.rows < 0) return hipErrorInvalidValue; \
+    if (sp->any_k && !any_k_ok(sp)) return hipErrorInvalidValue;                                        \
     const unsigned nb0 = (unsigned)((as.rows + kCplRows - 1) / kCplRows);                              \
     const unsigned nb = nb0 + (unsigned)((ad.rows + kCplRows - 1) / kCplRows);                         \
     if (nb == 0) return hipSuccess;                                                                     \
     const dim3 block(64 * kCplRows);                                                                    \
+    if (sp->any_k) {                                                                                    \
+        hipLaunchKernelGGL(KERNEL##_any_kernel, dim3(nb), block, 0, st, (int)sp->K, __VA_ARGS__, nb0);  \
+        return hipGetLastError();                                                                       \
+    }                                                                                                   \
     switch (sp->K) {                                                                                    \
-    case 5: hipLaunchKernelGGL((KERNEL<5>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;           \
-    case 8: hipLaunchKernelGGL((KERNEL<8>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;           \
-    case 15: hipLaunchKernelGGL((KERNEL<15>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;         \
-    case 32: hipLaunchKernelGGL((KERNEL<32>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;         \
+    case 5: hipLaunchKernelGGL((KERNEL##_kernel<5>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;   \
+    case 8: hipLaunchKernelGGL((KERNEL##_kernel<8>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;   \
+    case 15: hipLaunchKernelGGL((KERNEL##_kernel<15>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break; \
+    case 32: hipLaunchKernelGGL((KERNEL##_kernel<32>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break; \
     default: return hipErrorInvalidValue;                                                               \
     }                                                                                                   \
     return hipGetLastError();
@@ -1433,7 +1965,7 @@ hipError_t fs_coupling_pair_pre_impl(const fs_coupling *sp, const float *z, cons
                                      const float *ud, float *t, float *out, float *lad_u, int32_t *nan_flag,
                                      const fs_coupling *dp, const float *x, float *td, hipStream_t st) {
     const SamplePreArgs s{z, uw, uh, ud, t, out, lad_u, nan_flag};
-    FS_PAIR_LAUNCH(coupling_pair_pre_kernel, as, s, ad, x, td)
+    FS_PAIR_LAUNCH(coupling_pair_pre, as, s, ad, x, td)
 }
 
 hipError_t fs_coupling_pair_post_impl(const fs_coupling *sp, const float *params, const float *lad_u,
@@ -1443,9 +1975,8 @@ hipError_t fs_coupling_pair_post_impl(const fs_coupling *sp, const float *params
                                       float *lq_out_d, hipStream_t st) {
     const SamplePostArgs s{params, lad_u, lq_in, out, lq_out, nan_flag};
     const DensityFwdArgs d{x, params_d, uw, uh, ud, lq_in_d, out_d, lq_out_d};
-    FS_PAIR_LAUNCH(coupling_pair_post_kernel, as, s, ad, d)
+    FS_PAIR_LAUNCH(coupling_pair_post, as, s, ad, d)
 }
-#undef FS_PAIR_LAUNCH
 
 hipError_t fs_coupling_pair_step_impl(const fs_coupling *sp, const float *params, const float *lad_u,
                                       const float *lq_in, float *out, float *lq_out, int32_t *nan_flag,
@@ -1461,26 +1992,17 @@ hipError_t fs_coupling_pair_step_impl(const fs_coupling *sp, const float *params
     if (sp2->K != sp->K || as2.rows != sp->rows || ad2.rows != dp->rows || sp->D > kCplMaxD || dp->D > kCplMaxD ||
         sp2->D != sp->D || dp2->D != dp->D)
         return hipErrorInvalidValue;
-#define FS_PAIR_LAUNCH(KERNEL, ...)                                                                     \
-    const fs::CouplingArgs as = coupling_args(sp), ad = coupling_args(dp);                              \
-    if (sp->K != dp->K || as.rows < 0 || ad.rows < 0) return hipErrorInvalidValue;                     \
-    const unsigned nb0 = (unsigned)((as.rows + kCplRows - 1) / kCplRows);                              \
-    const unsigned nb = nb0 + (unsigned)((ad.rows + kCplRows - 1) / kCplRows);                         \
-    if (nb == 0) return hipSuccess;                                                                     \
-    const dim3 block(64 * kCplRows);                                                                    \
-    switch (sp->K) {                                                                                    \
-    case 5: hipLaunchKernelGGL((KERNEL<5>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;           \
-    case 8: hipLaunchKernelGGL((KERNEL<8>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;           \
-    case 15: hipLaunchKernelGGL((KERNEL<15>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;         \
-    case 32: hipLaunchKernelGGL((KERNEL<32>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;         \
-    default: return hipErrorInvalidValue;                                                               \
-    }                                                                                                   \
-    return hipGetLastError();
     if (coupling_waves() && sp->rows + dp->rows <= 0x7fffffff) {  // one row per two-wave workgroup
         const fs::CouplingArgs as = coupling_args(sp), ad = coupling_args(dp);
-        if (sp->K != dp->K || as.rows < 0 || ad.rows < 0) return hipErrorInvalidValue;
+        if (sp->K != dp->K || !sp->any_k != !dp->any_k || as.rows < 0 || ad.rows < 0) return hipErrorInvalidValue;
+        if (sp->any_k && !any_k_ok(sp)) return hipErrorInvalidValue;
         const unsigned nb0 = (unsigned)as.rows, nb = nb0 + (unsigned)ad.rows;
         if (nb == 0) return hipSuccess;
+        if (sp->any_k) {
+            hipLaunchKernelGGL(coupling_pair_step2_any_kernel, dim3(nb), dim3(128), 0, st, (int)sp->K, as, s, as2, s2,
+                               ad, d, ad2, t_d2, nb0);
+            return hipGetLastError();
+        }
         switch (sp->K) {
         case 5: hipLaunchKernelGGL(coupling_pair_step2_kernel<5>, dim3(nb), dim3(128), 0, st, as, s, as2, s2, ad, d, ad2, t_d2, nb0); break;
         case 8: hipLaunchKernelGGL(coupling_pair_step2_kernel<8>, dim3(nb), dim3(128), 0, st, as, s, as2, s2, ad, d, ad2, t_d2, nb0); break;
@@ -1490,9 +2012,9 @@ hipError_t fs_coupling_pair_step_impl(const fs_coupling *sp, const float *params
         }
         return hipGetLastError();
     }
-    FS_PAIR_LAUNCH(coupling_pair_step_kernel, as, s, as2, s2, ad, d, ad2, t_d2)
-#undef FS_PAIR_LAUNCH
+    FS_PAIR_LAUNCH(coupling_pair_step, as, s, as2, s2, ad, d, ad2, t_d2)
 }
+#undef FS_PAIR_LAUNCH
 
 hipError_t fs_coupling_features_fwd_impl(const fs_coupling *cp, const float *x, float *t, hipStream_t st) {
     const fs::CouplingArgs a = coupling_args(cp);

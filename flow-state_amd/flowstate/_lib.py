@@ -35,6 +35,7 @@ class Phys(ctypes.Structure):
 class Coupling(ctypes.Structure):
     """fs_coupling (include/flowstate.h)."""
     _fields_ = [("rows", ctypes.c_int64), ("D", ctypes.c_int32), ("K", ctypes.c_int32), ("hidden", ctypes.c_int32),
+                ("any_k", ctypes.c_int32),  # non-zero: the runtime-K kernels, 1 <= K <= 32
                 ("identity_features", ctypes.c_void_p), ("transform_features", ctypes.c_void_p),
                 ("tail_bound", ctypes.c_double)]
 

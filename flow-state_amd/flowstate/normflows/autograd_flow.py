@@ -176,6 +176,9 @@ def check_nan_flags():
 
 
 _HIP_K = (5, 8, 15, 32)
+# test hook: every fused coupling launch on the runtime-K kernels (fs_coupling.any_k), also
+# at an instantiated K, so the two kernel families can be A/B-tested on the same flow
+_force_any_k = False
 
 
 class _CircularRQS(torch.autograd.Function):
@@ -926,6 +929,7 @@ def _coupling_desc(layer, rows):
     c.D = layer.num_input_channels
     c.K = layer.num_bins
     c.hidden = layer.num_hidden_channels
+    c.any_k = int(_force_any_k or (_any_k(layer) and layer.num_bins not in _HIP_K))
     c.identity_features = p.identity_features.data_ptr()
     c.transform_features = p.transform_features.data_ptr()
     c.tail_bound = layer.tail_bound
@@ -946,10 +950,12 @@ def _check_shapes(layer, rows, params, uw, uh, ud):
 
 
 def fused_coupling_ok(layer, x):
-    """Device f32 rows, an instantiated K, index buffers on the same device."""
+    """Device f32 rows, an instantiated K (general-shape mode: any K in 1..32, on the
+    runtime-K kernels), index buffers on the same device."""
     p = layer.prqct
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == layer.num_input_channels
-            and layer.num_bins in _HIP_K and p.identity_features.device == x.device
+            and (layer.num_bins in _HIP_K or (_any_k(layer) and 1 <= layer.num_bins <= 32))
+            and p.identity_features.device == x.device
             and p.identity_features.dtype == torch.int64 and p.transform_features.dtype == torch.int64)
 
 

@@ -239,8 +239,10 @@ class NormalizingFlow(nn.Module):
         hidden width up to 512 and any bin count up to 32 (N <= 64): the mode for flows whose
         (hidden units, bins) pair the library does not instantiate, which the other modes
         refuse.  It is valid at instantiated shapes too, but those run faster in the default
-        mode (DESIGN.md 'General-shape mode').  In this mode forward_kld / reverse_kld also
-        train at any bin count, layer by layer (autograd_flow.circular_rqs any_k).
+        mode (DESIGN.md 'General-shape mode').  In this mode forward_kld / reverse_kld, the
+        shared-launch step, GraphedTrainStep and Algorithm2 also train at any bin count up to
+        32, on the fused coupling kernels with K a run-time value (fs_coupling.any_k); hidden
+        widths above 256 keep the fused coupling launches but stay off the shared-launch step.
         Returns self."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")

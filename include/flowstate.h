@@ -531,10 +531,17 @@ int fs_bn_relu_train_bwd(int64_t Bn, int32_t H, const float *x, const float *y, 
  * [rows][D] f32 row-major; identity_features / transform_features [D/2] int64 (the
  * layer's buffers); params [rows][D/2][3K+1] = the conditioner output; uw, uh [D/2][K],
  * ud [D/2][K+1] = the unconditional spline; t [rows][D] = [cos(s x_id), sin(s x_id)],
- * s = pi / tail_bound; hidden = the conditioner width (params / sqrt(hidden)). */
+ * s = pi / tail_bound; hidden = the conditioner width (params / sqrt(hidden)).
+ * any_k = 0: K must be one of the instantiated bin counts (5, 8, 15, 32), anything else is
+ * FS_EINVAL.  any_k != 0: every fs_coupling_* entry point runs its kernels with K as a
+ * run-time value, 1 <= K <= 32 (also at 5, 8, 15, 32: the same operations in the same
+ * order, slower than the instantiated kernels), the general-shape mode's training step.
+ * Entry points that take several descriptors need the same any_k and K on all of them.
+ * The field fills what was padding, so the struct keeps its 48 bytes and offsets. */
 typedef struct fs_coupling {
     int64_t rows;
     int32_t D, K, hidden;
+    int32_t any_k;
     const int64_t *identity_features, *transform_features;
     double tail_bound;
 } fs_coupling;
