@@ -509,6 +509,8 @@ int fs_rqs_backward_any(int64_t M, int32_t K, int32_t inverse, const float *x, c
 }
 
 int64_t fs_set_wide_rows(int64_t rows) { return fs_set_wide_rows_impl(rows); }
+int64_t fs_set_general_wide_rows(int64_t rows) { return fs_set_general_wide_rows_impl(rows); }
+int64_t fs_general_wide_passes(void) { return fs_general_wide_passes_impl(); }
 int32_t fs_set_wide_trunk16(int32_t on) { return fs_set_wide_trunk16_impl(on); }
 int32_t fs_set_wide_final32(int32_t on) { return fs_set_wide_final32_impl(on); }
 int64_t fs_set_wide_handoff_spins(int64_t spins) { return fs_set_wide_handoff_spins_impl(spins); }

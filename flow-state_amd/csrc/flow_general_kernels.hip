@@ -23,12 +23,17 @@
 //     wave take two different features of the same 32 chains.
 // A row's result depends on its own inputs only and every reduction has a fixed order,
 // so it is bit-identical whatever the batch size and the row's position.  No host
-// synchronisation, no allocation, no global scratch: capture-safe.
+// synchronisation, no allocation, no global scratch: capture-safe.  Small batches run the
+// same pass phase by phase on 32-row tiles ("Wide path" below), bit-identical.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <atomic>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "flow_device.h"
 #include "flow_layout.h"
@@ -506,6 +511,299 @@ __global__ void __launch_bounds__(kThreads) flow_general_kernel(FlowArgs a, int 
 }
 
 // ---------------------------------------------------------------------------
+// Wide path (small batches): the same pass phase by phase over the whole batch
+// ---------------------------------------------------------------------------
+// The fused kernel launches ceil(B / R) workgroups, 16 for a 1000-row batch at R = 64.
+// The wide path runs each coupling layer as two launches over 32-row tiles (a trunk
+// launch per tile, a final-layer launch per tile and group of kGenWideFeat transform
+// features) and ends with an output launch, 2 L + 1 launches, with the coordinates, the
+// trunk output and the log-det terms in a global workspace between them:
+//   CO  [rows][2N]   coordinates (physical order; the half-roll stays the `off` argument)
+//   X   [rows][Hp]   the trunk output h + s_h of the current layer
+//   TC  [rows][N]    the current layer's conditional log-det terms, one per feature
+//   TU  [rows][16]   (density) the current layer's unconditional slot sums
+//   LDP [rows][16]   the fused kernel's per-(chain, slot) log-det partials
+// Every value is computed by the fused kernel's own device functions on the same operands
+// (an MFMA tile element depends on its own row and column only, the spline is per chain
+// and feature), and the log-det is summed in the fused kernel's order: slot q = wid S + sub
+// of a chain (S = 64 / gen_rows(Hp), the FLOW's S, not the 32-row tile's) accumulates
+// from +0, layer by layer, the unconditional slot sum and the conditional terms of
+// features q, q + 8 S, ...; the output launch adds the 8 S slots in slot order.  The
+// fold of a layer's terms into LDP runs in the next trunk launch's prologue (the output
+// launch for the last layer).  So the results are bit-identical to flow_general_kernel's.
+constexpr int kGenWideRows = 32;       // rows per tile
+constexpr int kGenWideSlots = 16;      // 8 S <= 16 log-det slots per chain
+constexpr int kGenWideFinalWaves = 4;  // waves per final-launch workgroup
+constexpr int kGenWideFeat = 2 * kGenWideFinalWaves;  // transform features per final-launch workgroup
+
+struct GenWideArgs {
+    FlowArgs a;
+    float *CO, *X, *TC, *TU, *LDP;
+    int H;
+    int layer;  // packed layer of this launch
+    int off;    // coordinate offset (half-roll) of this launch
+    int first;  // first step of the pass: inputs instead of workspace coordinates, no fold
+};
+
+// LDP of (chain, slot) after folding in one layer's terms, in the fused kernel's order
+template <bool INV>
+__device__ __forceinline__ float gen_wide_fold(float p, const float *__restrict__ tc, const float *__restrict__ tu,
+                                               int N, int slot, int step) {
+    for (int j = slot; j < N; j += step) p += tc[j];
+    if (!INV) p += tu[slot];
+    return p;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(kThreads) gen_wide_trunk_kernel(GenWideArgs w) {
+    constexpr bool INV = MODE != MODE_DENSITY;
+    constexpr int R = kGenWideRows;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const FlowArgs &a = w.a;
+    const int N = a.N, D = 2 * N, K = a.K, H = w.H;
+    const GenLayout GL = gen_layout(N, H, a.nb, K);
+    const GenLds LL = gen_lds(N, GL.Hp, GL.kin_p, R);
+    const int XS = LL.xs, cs = LL.cstride;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = lane >> 5, r = lane & 31;
+    float *X = (float *)(smem + LL.x);
+    float *CO = (float *)(smem + LL.coord);
+    const int64_t row0 = (int64_t)blockIdx.x * R;
+    // log-det slots of the flow's own fused arrangement: S = 2 (flow R = 32): the lane halves
+    // are slots 2 wid, 2 wid + 1; S = 1 (flow R = 64): slot wid, on the lower lane half
+    const int S = 64 / GL.rows;
+    const int chain = r;
+    const int slot = wid * S + (S == 2 ? h : 0), step = kWaves * S;
+    const bool slot_on = S == 2 || h == 0;
+    const bool row_valid = row0 + chain < a.nrows;
+    // trunk: one row tile, column tile t = wid * tpw + s
+    const int tpw = GL.ct_h > kWaves ? 2 : 1;
+    bool tv[2];
+    int tct[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int t = wid * tpw + s;
+        tv[s] = s < tpw && t < GL.ct_h;
+        tct[s] = tv[s] ? t : 0;
+    }
+
+    // ---- coordinates -> CO: the pass inputs (flow_general_kernel's input phase) or the workspace
+    if (w.first && MODE == MODE_PROPOSE) {
+        const int nq = (D + 3) / 4;
+        for (int e = tid; e < R * nq; e += kThreads) {
+            const int rr = e / nq, q = e - rr * nq;
+            const int64_t lr = row0 + rr, rpc = a.rows_per_counter;
+            const uint64_t ctr = rpc > 0 ? a.counter + (uint64_t)(lr / rpc) : a.counter;
+            const uint64_t gr = (uint64_t)(a.row_offset + (rpc > 0 ? lr % rpc : lr));
+            uint4 c = make_uint4((uint32_t)gr, (uint32_t)(gr >> 32) ^ (uint32_t)(ctr >> 32), (uint32_t)ctr,
+                                 (uint32_t)q);
+            uint4 o = philox4x32(c, make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32)));
+            const uint32_t u4[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int i = 4 * q + t;
+                if (i < D) {
+                    const float u = (float)(u4[t] >> 8) * 5.9604644775390625e-08f;  // [0,1)
+                    CO[rr * cs + i] = u * a.twoB + a.negB;
+                }
+            }
+        }
+    } else if (w.first) {
+        for (int e = tid; e < R * D; e += kThreads) {
+            const int rr = e / D, i = e - rr * D;
+            const int64_t gr = row0 + rr;
+            CO[rr * cs + i] = (gr < a.nrows) ? a.in[gr * D + i] : 0.f;
+        }
+    } else {
+        for (int e = tid; e < R * D; e += kThreads) {
+            const int rr = e / D, i = e - rr * D;
+            CO[rr * cs + i] = w.CO[(row0 + rr) * D + i];
+        }
+    }
+    bool nan_any = false;
+    const int off = w.off;
+    const float *P = a.packed + (int64_t)w.layer * GL.stride;
+    const float *V = P + GL.vec;
+    __syncthreads();
+
+    // ---- log-det partial of (chain, slot): fold the previous layer, then (sampling
+    // direction) this layer's unconditional spline on the identity features
+    float ldp = 0.f;
+    if (slot_on && !w.first)
+        ldp = gen_wide_fold<INV>(w.LDP[(row0 + chain) * kGenWideSlots + slot], w.TC + (row0 + chain) * N,
+                                 w.TU + (row0 + chain) * kGenWideSlots, N, slot, step);
+    if (INV) {
+        if (slot_on) ldp += gen_uncond_spline<true>(P + GL.unc, CO, cs, N, D, off, K, a, nan_any, slot, step, chain);
+        __syncthreads();
+    }
+    if (slot_on) w.LDP[(row0 + chain) * kGenWideSlots + slot] = ldp;
+
+    // periodic features -> X, zero pad to kin_p
+    for (int e = tid; e < R * N; e += kThreads) {
+        const int rr = e / N, f = e - rr * N;
+        const float sv = a.scale_pf * CO[rr * cs + (2 * f + off) % D];
+        X[rr * XS + f] = cosf(sv);
+        X[rr * XS + N + f] = sinf(sv);
+    }
+    const int npad = GL.kin_p - D;
+    for (int e = tid; e < R * npad; e += kThreads) {
+        const int rr = e / npad, c = e - rr * npad;
+        X[rr * XS + D + c] = 0.f;
+    }
+    __syncthreads();
+    if (!INV) {
+        // density direction: the layer's unconditional spline acts on the identity features
+        // only, after the conditioner has read them; its slot sum is folded after the
+        // layer's conditional terms
+        if (slot_on)
+            w.TU[(row0 + chain) * kGenWideSlots + slot] =
+                gen_uncond_spline<false>(P + GL.unc, CO, cs, N, D, off, K, a, nan_any, slot, step, chain);
+    }
+    if (nan_any && row_valid && a.err) atomicOr(a.err, 1);
+
+    // ResidualNet: flow_general_kernel's R = 32 arrangement
+    f32x16 hr[2], acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) hr[t][i] = 0.f;
+        if (tv[t]) gen_gemm_tile<false>(X, XS, P + GL.win + (int64_t)tct[t] * GL.kg_in * 256, GL.kg_in, 0, hr[t]);
+    }
+    for (int jb = 0; jb < a.nb; ++jb) {
+        const float *VB = V + GL.v_blocks + (int64_t)4 * H * jb;
+        const float *W0 = P + GL.blocks + jb * GL.block_stride;
+        const float *W1 = W0 + GL.block_stride / 2;
+        __syncthreads();  // every wave has read X
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (tv[t]) {
+                const int col = 32 * tct[t] + r;
+                const bool on = col < H;
+                const float e0 = on ? VB[col] : 0.f, e1 = on ? VB[H + col] : 0.f;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) X[acc_row(0, i, h) * XS + col] = fmaxf(fmaf(hr[t][i], e0, e1), 0.f);
+            }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+            if (tv[t]) gen_gemm_tile<false>(X, XS, W0 + (int64_t)tct[t] * GL.kg_h * 256, GL.kg_h, 0, acc[t]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (tv[t]) {
+                const int col = 32 * tct[t] + r;
+                const bool on = col < H;
+                const float e2 = on ? VB[2 * H + col] : 0.f, e3 = on ? VB[3 * H + col] : 0.f;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) X[acc_row(0, i, h) * XS + col] = fmaxf(fmaf(acc[t][i], e2, e3), 0.f);
+            }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (tv[t]) gen_gemm_tile<false>(X, XS, W1 + (int64_t)tct[t] * GL.kg_h * 256, GL.kg_h, 0, hr[t]);
+    }
+    // h (+ the deferred biases) -> workspace X for the final launch
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+        if (tv[t]) {
+            const int col = 32 * tct[t] + r;
+            const float sh = col < H ? V[col] : 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) w.X[(row0 + acc_row(0, i, h)) * GL.Hp + col] = hr[t][i] + sh;
+        }
+    // coordinates -> workspace (the inputs on the first step, the identity features the
+    // unconditional spline moved on every step)
+    __syncthreads();
+    for (int e = tid; e < R * D; e += kThreads) {
+        const int rr = e / D, i = e - rr * D;
+        w.CO[(row0 + rr) * D + i] = CO[rr * cs + i];
+    }
+}
+
+// Final layer + conditional spline: blockIdx.x = 32-row tile, blockIdx.y = group of
+// kGenWideFeat transform features, two per wave on the lane halves (gen_cond_spline's
+// S == 2 form).  One writer per (row, feature) coordinate and log-det term.
+template <bool INV>
+__global__ void __launch_bounds__(64 * kGenWideFinalWaves) gen_wide_final_kernel(GenWideArgs w) {
+    constexpr int R = kGenWideRows;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const FlowArgs &a = w.a;
+    const int N = a.N, D = 2 * N, K = a.K;
+    const GenLayout GL = gen_layout(N, w.H, a.nb, K);
+    const int XS = GL.Hp + 4;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = lane >> 5, chain = lane & 31;
+    float *X = (float *)smem;
+    const int64_t row0 = (int64_t)blockIdx.x * R;
+    const int q4 = GL.Hp / 4;
+    for (int e = tid; e < R * q4; e += 64 * kGenWideFinalWaves) {
+        const int rr = e / q4, q = e - rr * q4;
+        *(f32x4 *)(X + rr * XS + 4 * q) = *(const f32x4 *)(w.X + (row0 + rr) * GL.Hp + 4 * q);
+    }
+    __syncthreads();
+    const int j0 = blockIdx.y * kGenWideFeat + 2 * wid;
+    if (j0 >= N) return;
+    const int f0 = j0, f1 = j0 + 1 < N ? j0 + 1 : j0;
+    const int jraw = j0 + h;
+    const bool act = jraw < N;
+    const int jl = act ? jraw : N - 1;
+    bool nan_any = false;
+    const float *P = a.packed + (int64_t)w.layer * GL.stride;
+    const float l = gen_cond_spline<INV>(X, XS, P, GL, f0, f1, 0, jl, act, chain, w.CO + row0 * D, D,
+                                         (2 * jl + 1 + w.off) % D, K, a, nan_any);
+    if (act) w.TC[(row0 + chain) * N + jl] = l;
+    if (nan_any && row0 + chain < a.nrows && a.err) atomicOr(a.err, 1);
+}
+
+// Output phase: fold the last layer, add a chain's slots in slot order, write the results
+// (flow_general_kernel's output phase).  One thread per row for the scalar, all for `out`.
+template <int MODE>
+__global__ void __launch_bounds__(256) gen_wide_output_kernel(GenWideArgs w) {
+    constexpr bool INV = MODE != MODE_DENSITY;
+    constexpr int R = kGenWideRows;
+    const FlowArgs &a = w.a;
+    const int N = a.N, D = 2 * N;
+    const int tid = threadIdx.x, off = w.off;
+    const int64_t row0 = (int64_t)blockIdx.x * R;
+    const int nslots = kWaves * (64 / gen_rows((int)rup(w.H, 32)));
+    if (tid < R && row0 + tid < a.nrows) {
+        const int64_t gr = row0 + tid;
+        float tot = 0.f;
+        for (int q = 0; q < nslots; ++q)
+            tot += gen_wide_fold<INV>(w.LDP[gr * kGenWideSlots + q], w.TC + gr * N, w.TU + gr * kGenWideSlots, N, q,
+                                      nslots);
+        float outv = tot;
+        if (MODE == MODE_DENSITY && a.add_base) {
+            bool inb = true;
+            for (int i = 0; i < D; ++i) {
+                const float z = w.CO[gr * D + i];
+                inb = inb && (z >= a.negB) && (z <= a.B);
+            }
+            outv = tot + (inb ? a.base_lp : -INFINITY);
+        }
+        if (MODE == MODE_PROPOSE && a.add_base) outv = a.base_lp - tot;
+        if (a.scalar_out) a.scalar_out[gr] = outv;
+    }
+    for (int e = tid; e < R * D; e += 256) {
+        const int rr = e / D, i = e - rr * D;
+        const int64_t gr = row0 + rr;
+        if (gr >= a.nrows) continue;
+        const float v = w.CO[gr * D + (i + off) % D];
+        if (a.out) a.out[gr * D + i] = v;
+        if (MODE == MODE_PROPOSE) {
+            const float cfg = v + a.B;
+            if (a.config) a.config[gr * D + i] = cfg;
+            if (a.centered) a.centered[gr * D + i] = (float)((double)cfg - a.half_width);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Packing
 // ---------------------------------------------------------------------------
 // Fragments of a Linear W[nout][kin] for all layers (blockIdx.y) and blocks (blockIdx.z);
@@ -659,8 +957,154 @@ static hipError_t launch_general(const FlowArgs &a, int N, int H, hipStream_t st
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// wide path: host side
+// ---------------------------------------------------------------------------
+constexpr int64_t kGenWideMaxRows = 65536;  // the workspace never grows beyond this many rows
+// the measured default (tools/general_wide_ab.py, DESIGN.md 'General-shape mode'): the largest
+// row count at which the wide path beat the fused kernel at every measured shape
+#ifndef FS_GENERAL_WIDE_ROWS_DEFAULT
+#define FS_GENERAL_WIDE_ROWS_DEFAULT 1024
+#endif
+
+// Largest batch that takes the wide path (FS_GENERAL_WIDE_ROWS, or
+// fs_set_general_wide_rows(); 0 disables it)
+static std::atomic<int64_t> g_gen_wide_rows{-1};
+static std::atomic<int64_t> g_gen_wide_passes{0};
+static int64_t gen_wide_rows_limit() {
+    int64_t lim = g_gen_wide_rows.load(std::memory_order_relaxed);
+    if (lim < 0) {
+        const char *e = getenv("FS_GENERAL_WIDE_ROWS");
+        lim = e ? atoll(e) : FS_GENERAL_WIDE_ROWS_DEFAULT;
+        lim = lim < 0 ? 0 : (lim > kGenWideMaxRows ? kGenWideMaxRows : lim);
+        int64_t expect = -1;
+        g_gen_wide_rows.compare_exchange_strong(expect, lim);
+        lim = g_gen_wide_rows.load(std::memory_order_relaxed);
+    }
+    return lim;
+}
+
+int64_t fs_set_general_wide_rows_impl(int64_t rows) {
+    const int64_t prev = gen_wide_rows_limit();
+    if (rows >= 0) g_gen_wide_rows.store(rows > kGenWideMaxRows ? kGenWideMaxRows : rows, std::memory_order_relaxed);
+    return prev;
+}
+
+int64_t fs_general_wide_passes_impl() { return g_gen_wide_passes.load(std::memory_order_relaxed); }
+
+// Workspace of the general wide path, one per (device, stream), allocated once (never
+// freed or moved: a captured graph may hold its address).  nullptr when it would have to
+// be allocated during stream capture or the first allocation (of `cap` bytes) is smaller
+// than the `bytes` this pass needs.
+static void *gen_wide_workspace(size_t bytes, size_t cap, hipStream_t st) {
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, std::pair<void *, size_t>> ws;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> g(mu);
+    auto &e = ws[{dev, st}];
+    if (e.first && e.second >= bytes) return e.first;
+    if (e.first) return nullptr;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
+    void *p = nullptr;
+    if (hipMalloc(&p, cap) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    e = {p, cap};
+    return p;
+}
+
+// compute units of the current device (cached per device)
+static int gen_device_cus() {
+    static std::atomic<int> cus[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int v = cus[dev].load(std::memory_order_relaxed);
+    if (v <= 0) {
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        cus[dev].store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
+
+// CO, X, TC, TU, LDP of R rows (a multiple of 32), each section 256-byte aligned
+static size_t gen_wide_bytes(int64_t R, int N, int Hp) {
+    return (size_t)(rup(R * 2 * N * 4, 256) + rup(R * Hp * 4, 256) + rup(R * N * 4, 256) +
+                    2 * rup(R * kGenWideSlots * 4, 256));
+}
+
+// The pass as 2 L + 1 launches on the stream; used = false (and nothing launched) when the
+// workspace is not available or too small: the caller then launches the fused kernel.
+template <int MODE>
+static hipError_t gen_wide_pass(const FlowArgs &a, int N, int H, hipStream_t st, bool &used) {
+    constexpr bool INV = MODE != MODE_DENSITY;
+    used = false;
+    const GenLayout GL = gen_layout(N, H, a.nb, a.K);
+    const int64_t R = rup(a.nrows, kGenWideRows);
+    // one allocation per (device, stream), sized for at least 16384 rows at the widest shape
+    // (~46 MiB) or the current limit if larger
+    const int64_t lim = gen_wide_rows_limit() < 16384 ? 16384 : gen_wide_rows_limit();
+    const size_t cap = gen_wide_bytes(rup(lim, kGenWideRows), kMaxN, kGenMaxH);
+    const size_t need = gen_wide_bytes(R, N, GL.Hp);
+    if (need > cap) return hipSuccess;
+    char *p = (char *)gen_wide_workspace(need, cap, st);
+    if (!p) return hipSuccess;
+    auto ktr = gen_wide_trunk_kernel<MODE>;
+    auto kfi = gen_wide_final_kernel<INV>;
+    {
+        static std::atomic<unsigned long long> tr_set{0}, fi_set{0};  // per instantiation, bit d = device d
+        if (hipError_t e = fs_set_max_lds_once((const void *)ktr, tr_set); e != hipSuccess) return e;
+        if (hipError_t e = fs_set_max_lds_once((const void *)kfi, fi_set); e != hipSuccess) return e;
+    }
+    const int D = 2 * N;
+    GenWideArgs w;
+    memset(&w, 0, sizeof(w));
+    w.a = a;
+    w.H = H;
+    w.CO = (float *)p;
+    p += rup(R * D * 4, 256);
+    w.X = (float *)p;
+    p += rup(R * GL.Hp * 4, 256);
+    w.TC = (float *)p;
+    p += rup(R * N * 4, 256);
+    w.TU = (float *)p;
+    p += rup(R * kGenWideSlots * 4, 256);
+    w.LDP = (float *)p;
+    const unsigned tiles = (unsigned)(R / kGenWideRows);
+    const unsigned groups = (unsigned)((N + kGenWideFeat - 1) / kGenWideFeat);
+    const unsigned tr_lds = (unsigned)gen_lds(N, GL.Hp, GL.kin_p, kGenWideRows).total;
+    const unsigned fi_lds = (unsigned)(kGenWideRows * (GL.Hp + 4) * 4);
+    int off = 0;
+    for (int s = 0; s < a.L; ++s) {
+        w.layer = INV ? s : a.L - 1 - s;
+        if (INV) off = (off + N) % D;  // Coupling.inverse rolls first
+        w.off = off;
+        w.first = s == 0;
+        hipLaunchKernelGGL(ktr, dim3(tiles), dim3(kThreads), tr_lds, st, w);
+        hipLaunchKernelGGL(kfi, dim3(tiles, groups), dim3(64 * kGenWideFinalWaves), fi_lds, st, w);
+        if (!INV) off = (off + N) % D;  // Coupling.forward rolls last
+    }
+    w.off = off;
+    w.first = 0;
+    hipLaunchKernelGGL(gen_wide_output_kernel<MODE>, dim3(tiles), dim3(256), 0, st, w);
+    used = true;
+    g_gen_wide_passes.fetch_add(1, std::memory_order_relaxed);
+    return hipGetLastError();
+}
+
 hipError_t fs_flow_general_pass(const FlowArgs &a, int mode, int N, int H, int K, hipStream_t st) {
     (void)K;
+    const int R = gen_rows((int)rup(H, 32));
+    if (a.nrows <= gen_wide_rows_limit() && (a.nrows + R - 1) / R < 2 * gen_device_cus()) {
+        // small batch: the wide path (bit-identical results), when its workspace is available
+        bool used = false;
+        hipError_t e = mode == MODE_DENSITY  ? gen_wide_pass<MODE_DENSITY>(a, N, H, st, used)
+                       : mode == MODE_SAMPLE ? gen_wide_pass<MODE_SAMPLE>(a, N, H, st, used)
+                                             : gen_wide_pass<MODE_PROPOSE>(a, N, H, st, used);
+        if (e != hipSuccess || used) return e;
+    }
     if (mode == MODE_DENSITY) return launch_general<MODE_DENSITY>(a, N, H, st);
     if (mode == MODE_SAMPLE) return launch_general<MODE_SAMPLE>(a, N, H, st);
     return launch_general<MODE_PROPOSE>(a, N, H, st);

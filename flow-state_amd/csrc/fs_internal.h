@@ -75,6 +75,8 @@ hipError_t fs_rqs_backward_any_impl(int64_t M, int K, int inverse, const float *
                                     const float *ud, float B, const float *g_out, const float *g_lad, float *gx,
                                     float *guw, float *guh, float *gud, hipStream_t st);
 int64_t fs_set_wide_rows_impl(int64_t rows);
+int64_t fs_set_general_wide_rows_impl(int64_t rows);
+int64_t fs_general_wide_passes_impl();
 int32_t fs_set_wide_trunk16_impl(int32_t on);
 int32_t fs_set_wide_final32_impl(int32_t on);
 int64_t fs_set_wide_handoff_spins_impl(int64_t spins);

@@ -155,6 +155,8 @@ _SIGS = {
     "fs_coupling_pair_step": (ctypes.c_int, [_CP] + [_P] * 6 + [_CP] + [_P] * 6 + [_CP] + [_P] * 8 + [_CP, _P, _P]),
     "fs_coupling_pair_post": (ctypes.c_int, [_CP] + [_P] * 6 + [_CP] + [_P] * 9),
     "fs_set_wide_rows": (_I64, [_I64]),
+    "fs_set_general_wide_rows": (_I64, [_I64]),
+    "fs_general_wide_passes": (_I64, []),
     "fs_set_wide_trunk16": (ctypes.c_int32, [ctypes.c_int32]),
     "fs_set_wide_final32": (ctypes.c_int32, [ctypes.c_int32]),
     "fs_set_wide_handoff_spins": (_I64, [_I64]),

@@ -281,6 +281,19 @@ int fs_nf_mh_step_banked(const fs_flow_dims *d, const void *packed, const fs_phy
  * previous limit.  Process-wide. */
 int64_t fs_set_wide_rows(int64_t rows);
 
+/* The same for the general-shape mode (fs_flow_dims.precision = 4): the largest batch
+ * (rows) its passes run phase by phase on 32-row tiles (2 L + 1 launches over a
+ * per-stream workspace) instead of on flow_general_kernel's ceil(rows / 64 or 32)
+ * workgroups, bit-identical results.  Taken only while the fused grid is below twice the
+ * device's compute units and the workspace is available (it is never allocated during
+ * stream capture).  Default: the FS_GENERAL_WIDE_ROWS environment variable, else 1024
+ * (measured, DESIGN.md 'General-shape mode'); 0 disables it; capped at 65536; a negative argument only
+ * reads.  Returns the previous limit.  Process-wide, makes no HIP call. */
+int64_t fs_set_general_wide_rows(int64_t rows);
+/* Number of general-shape passes that took the wide path since the process started
+ * (monotonic, process-wide, no HIP call): which path ran, for tests and tools. */
+int64_t fs_general_wide_passes(void);
+
 /* Kernel-variant switches for A/B measurements and bit-identity tests, process-wide; each
  * returns the previous value (a negative argument only reads it).  The results do not
  * depend on them.
