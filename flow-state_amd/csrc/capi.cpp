@@ -542,6 +542,22 @@ int fs_kld_loss_backward(const float *grad_loss, int64_t B, float *grad_log_q, v
     return hip_rc(fs_kld_loss_bwd_impl(grad_loss, B, grad_log_q, (hipStream_t)stream), "fs_kld_loss_backward");
 }
 
+int fs_kld_loss_mix(const float *log_q, int64_t B, const float *energy, const float *lq_rev, int64_t R, double alpha,
+                    const int32_t *nan_word, float *loss, uint8_t *nan_out, void *stream) {
+    REQUIRE(B >= 1 && R >= 1 && log_q && energy && lq_rev && loss, "fs_kld_loss_mix: invalid arguments");
+    return hip_rc(fs_kld_loss_mix_impl(log_q, B, energy, lq_rev, R, alpha, nan_word, loss, nan_out,
+                                       (hipStream_t)stream),
+                  "fs_kld_loss_mix");
+}
+
+int fs_kld_loss_mix_backward(const float *grad_loss, int64_t B, int64_t R, double alpha, float *grad_log_q,
+                             float *grad_energy, float *grad_lq_rev, void *stream) {
+    REQUIRE(B >= 1 && R >= 1 && grad_loss, "fs_kld_loss_mix_backward: invalid arguments");
+    return hip_rc(fs_kld_loss_mix_bwd_impl(grad_loss, B, R, alpha, grad_log_q, grad_energy, grad_lq_rev,
+                                           (hipStream_t)stream),
+                  "fs_kld_loss_mix_backward");
+}
+
 int fs_target_energy(const float *x, int64_t B, int32_t N, double bound, double temperature, int32_t num_wells,
                      double V0_0, double V0_1, double r0, double k, float *E, float *grad_x, void *stream) {
     REQUIRE(B >= 0 && N >= 1 && N <= 1024 && bound > 0.0 && temperature > 0.0 && num_wells >= 0 && num_wells <= 2 &&
@@ -888,6 +904,44 @@ int fs_coupling_sample_post(const fs_coupling *c, const float *params, const flo
     REQUIRE(c->rows == 0 || (params && lad_u && out && lq_out), "fs_coupling_sample_post: invalid arguments");
     return hip_rc(fs_coupling_sample_post_impl(c, params, lad_u, lq_in, out, lq_out, nan_flag, (hipStream_t)stream),
                   "fs_coupling_sample_post");
+}
+
+int fs_coupling_sample_bwd_post(const fs_coupling *c, const float *z, const float *params, const float *g_out,
+                                const float *g_lq, float *gz, float *g_params, void *stream) {
+    int rc = check_coupling(c, "fs_coupling_sample_bwd_post");
+    if (rc) return rc;
+    REQUIRE(c->rows == 0 || (z && params && g_params), "fs_coupling_sample_bwd_post: invalid arguments");
+    return hip_rc(fs_coupling_sample_bwd_post_impl(c, z, params, g_out, g_lq, gz, g_params, (hipStream_t)stream),
+                  "fs_coupling_sample_bwd_post");
+}
+
+int fs_coupling_sample_bwd_pre(const fs_coupling *c, const float *z, const float *out, const float *uw,
+                               const float *uh, const float *ud, const float *g_t, const float *g_out,
+                               const float *g_lq, float *gz, float *g_u, void *stream) {
+    int rc = check_coupling(c, "fs_coupling_sample_bwd_pre");
+    if (rc) return rc;
+    REQUIRE(c->rows == 0 || (z && out && uw && uh && ud && g_t && g_u), "fs_coupling_sample_bwd_pre: invalid arguments");
+    return hip_rc(fs_coupling_sample_bwd_pre_impl(c, z, out, uw, uh, ud, g_t, g_out, g_lq, gz, g_u,
+                                                  (hipStream_t)stream),
+                  "fs_coupling_sample_bwd_pre");
+}
+
+int fs_coupling_sample_bwd_step(const fs_coupling *c, const float *z, const float *out, const float *uw,
+                                const float *uh, const float *ud, const float *g_t, const float *g_out,
+                                const float *g_lq, float *gz, float *g_u, const fs_coupling *prev, const float *z_prev,
+                                const float *params_prev, const float *g_lq_prev, float *gz_prev, float *g_params_prev,
+                                void *stream) {
+    int rc = check_coupling(c, "fs_coupling_sample_bwd_step");
+    if (rc || (rc = check_coupling(prev, "fs_coupling_sample_bwd_step"))) return rc;
+    REQUIRE(prev->rows == c->rows && prev->D == c->D && prev->K == c->K && !prev->any_k == !c->any_k && c->D <= 256,
+            "fs_coupling_sample_bwd_step: the layers differ in rows, D, K or any_k (D <= 256)");
+    REQUIRE(c->rows == 0 || (z && out && uw && uh && ud && g_t && gz && g_u && z_prev && params_prev && g_params_prev),
+            "fs_coupling_sample_bwd_step: invalid arguments");
+    REQUIRE(gz != gz_prev, "fs_coupling_sample_bwd_step: gz_prev must not alias gz");
+    return hip_rc(fs_coupling_sample_bwd_step_impl(c, z, out, uw, uh, ud, g_t, g_out, g_lq, gz, g_u, prev, z_prev,
+                                                   params_prev, g_lq_prev, gz_prev, g_params_prev,
+                                                   (hipStream_t)stream),
+                  "fs_coupling_sample_bwd_step");
 }
 
 int fs_coupling_pair_pre(const fs_coupling *s, const float *z, const float *uw, const float *uh, const float *ud,

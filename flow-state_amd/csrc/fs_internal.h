@@ -217,3 +217,18 @@ hipError_t fs_coupling_sample_post_impl(const fs_coupling *cp, const float *para
                                         hipStream_t st);
 hipError_t fs_coupling_features_bwd_impl(const fs_coupling *cp, const float *x, const float *g_t, float *gx,
                                          const float *gx_add, hipStream_t st);
+hipError_t fs_coupling_sample_bwd_post_impl(const fs_coupling *cp, const float *z, const float *params,
+                                            const float *g_out, const float *g_lq, float *gz, float *g_params,
+                                            hipStream_t st);
+hipError_t fs_coupling_sample_bwd_pre_impl(const fs_coupling *cp, const float *z, const float *out, const float *uw,
+                                           const float *uh, const float *ud, const float *g_t, const float *g_out,
+                                           const float *g_lq, float *gz, float *g_u, hipStream_t st);
+hipError_t fs_coupling_sample_bwd_step_impl(const fs_coupling *cp, const float *z, const float *out, const float *uw,
+                                            const float *uh, const float *ud, const float *g_t, const float *g_out,
+                                            const float *g_lq, float *gz, float *g_u, const fs_coupling *pp,
+                                            const float *z_prev, const float *params_prev, const float *g_lq_prev,
+                                            float *gz_prev, float *g_params_prev, hipStream_t st);
+hipError_t fs_kld_loss_mix_impl(const float *log_q, int64_t B, const float *E, const float *lq_rev, int64_t R,
+                                double alpha, const int32_t *nan_word, float *loss, uint8_t *nan_out, hipStream_t st);
+hipError_t fs_kld_loss_mix_bwd_impl(const float *g, int64_t B, int64_t R, double alpha, float *grad_log_q,
+                                    float *grad_energy, float *grad_lq_rev, hipStream_t st);

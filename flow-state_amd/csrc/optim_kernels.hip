@@ -138,6 +138,42 @@ __global__ void __launch_bounds__(256) kld_loss_bwd_kernel(const float *__restri
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < B; i += (int64_t)gridDim.x * 256) out[i] = v;
 }
 
+// The loss at any ALPHA (main_algorithm_2.py:316-318): a x (-mean log_q) + b x (mean E +
+// mean lq_rev), a = ALPHA and b = 1 - ALPHA as torch hands python floats to its float32
+// kernels; kld_loss_kernel's reduction and NaN word handling.
+__global__ void __launch_bounds__(256) kld_loss_mix_kernel(const float *__restrict__ log_q, int64_t B,
+                                                           const float *__restrict__ E,
+                                                           const float *__restrict__ lq_rev, int64_t R, float a,
+                                                           float b, const int32_t *__restrict__ nan_word,
+                                                           float *__restrict__ loss, uint8_t *__restrict__ nan_out) {
+    __shared__ float red[256];
+    const float sq = block_sum256(log_q, B, red);
+    const float se = block_sum256(E, R, red);
+    const float sl = block_sum256(lq_rev, R, red);
+    if (threadIdx.x == 0) {
+        const float sample = -(sq * (1.f / (float)B));
+        const float energy = se * (1.f / (float)R) + sl * (1.f / (float)R);
+        loss[0] = a * sample + b * energy;
+        if (nan_out) nan_out[0] = (nan_word && nan_word[0] != 0) ? 1 : 0;
+    }
+}
+
+// d loss / d log_q = -(g a) x (1 / B), d loss / d E = d loss / d lq_rev = (g b) x (1 / R) per
+// row (torch's MulBackward, NegBackward, MeanBackward); each output nullable
+__global__ void __launch_bounds__(256) kld_loss_mix_bwd_kernel(const float *__restrict__ g, int64_t B, int64_t R,
+                                                               float a, float b, float *__restrict__ gq,
+                                                               float *__restrict__ ge, float *__restrict__ gl) {
+    const float vq = (-(g[0] * a)) * (1.f / (float)B);
+    const float ve = (g[0] * b) * (1.f / (float)R);
+    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (gq)
+        for (int64_t i = i0; i < B; i += step) gq[i] = vq;
+    for (int64_t i = i0; i < R; i += step) {
+        if (ge) ge[i] = ve;
+        if (gl) gl[i] = ve;
+    }
+}
+
 }  // namespace fs
 
 using namespace fs;
@@ -171,5 +207,21 @@ hipError_t fs_kld_loss_impl(const float *log_q, int64_t B, const float *E, const
 hipError_t fs_kld_loss_bwd_impl(const float *g, int64_t B, float *grad_log_q, hipStream_t st) {
     const int64_t blocks = B / 256 + 1 < 64 ? B / 256 + 1 : 64;
     hipLaunchKernelGGL(kld_loss_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, B, grad_log_q);
+    return hipGetLastError();
+}
+
+hipError_t fs_kld_loss_mix_impl(const float *log_q, int64_t B, const float *E, const float *lq_rev, int64_t R,
+                                double alpha, const int32_t *nan_word, float *loss, uint8_t *nan_out, hipStream_t st) {
+    hipLaunchKernelGGL(kld_loss_mix_kernel, dim3(1), dim3(256), 0, st, log_q, B, E, lq_rev, R, (float)alpha,
+                       (float)(1.0 - alpha), nan_word, loss, nan_out);
+    return hipGetLastError();
+}
+
+hipError_t fs_kld_loss_mix_bwd_impl(const float *g, int64_t B, int64_t R, double alpha, float *grad_log_q,
+                                    float *grad_energy, float *grad_lq_rev, hipStream_t st) {
+    const int64_t n = B > R ? B : R;
+    const int64_t blocks = n / 256 + 1 < 64 ? n / 256 + 1 : 64;
+    hipLaunchKernelGGL(kld_loss_mix_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, B, R, (float)alpha,
+                       (float)(1.0 - alpha), grad_log_q, grad_energy, grad_lq_rev);
     return hipGetLastError();
 }

@@ -1729,6 +1729,236 @@ __global__ __launch_bounds__(256) void coupling_bwd_step4_any_kernel(
     density_bwd_row4_any(K, c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, kx);
 }
 
+// ---------------------------------------------------------------------------
+// Adjoints of the sampling direction (Coupling.inverse, coupling.py:104-134; reverse_kld,
+// core.py:105-142), in two launches around the conditioner's backward.  One wave per row,
+// lane = feature j (j += 64), as the forward kernels.  With zi = z[(id_j + split) % D],
+// yi = uinv(zi), t = [cos(s yi), sin(s yi)], params = C(t), xt = z[(tr_j + split) % D],
+// yt = cinv(xt; params) and lq_out = lq_in - (sum li + sum lt):
+//   bwd_post (before the conditioner's backward): the conditional inverse spline's adjoints
+//     from g_out at the transform positions and -g_lq: gz at (tr_j + split) % D and
+//     g_params [rows][n][3K+1] (widths and heights / sq), density_bwd_row's layout;
+//   bwd_pre (after it): g_yi = g_out at the identity position + the features' adjoint
+//     (features_bwd_row's expression on yi = out[id_j]), then the unconditional inverse
+//     spline's adjoints: gz at (id_j + split) % D and the per-row g_u [uw | uh | ud].
+// The two write disjoint halves of gz (nullable: the input needs no gradient).  gor: the
+// row of g_out (nullable = 0).  xt is read from the layer input z: post overwrote it in out.
+struct SampleBwdPostArgs {
+    const float *z, *params, *g_lq;
+    float *gz, *g_params;
+};
+
+struct SampleBwdPreArgs {
+    const float *z, *out, *uw, *uh, *ud, *g_t, *g_lq;
+    float *gz, *g_u;
+};
+
+template <int K>
+__device__ __forceinline__ void sample_bwd_post_row(const CouplingArgs &c, const SampleBwdPostArgs &s,
+                                                    const float *gor, int64_t row) {
+    const int lane = threadIdx.x & 63;
+    const float *zr = s.z + row * c.D;
+    const float gl = s.g_lq ? -s.g_lq[row] : 0.f;  // lq_out = lq_in - (... + lt)
+    constexpr int P = 3 * K + 1;
+    for (int j = lane; j < c.n; j += 64) {
+        const int pt = (int)c.tr[j];
+        const int qt = (pt + c.split) % c.D;
+        const float xt = zr[qt];
+        const float got = gor ? gor[pt] : 0.f;
+        float *gp = s.g_params + (row * c.n + j) * P;
+        float g = got;
+        if (xt >= -c.bound && xt <= c.bound) {
+            const float *p = s.params + (row * c.n + j) * P;
+            float w[K], h[K], gw[K], gh[K], gd[K + 1];
+            cond_params<K>(p, c.sq, w, h);
+            rqs_point_bwd<K, true>(xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, gd);
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                gp[k] = gw[k] / c.sq;
+                gp[K + k] = gh[k] / c.sq;
+            }
+#pragma unroll
+            for (int k = 0; k <= K; ++k) gp[2 * K + k] = gd[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < P; ++k) gp[k] = 0.f;
+        }
+        if (s.gz) s.gz[row * c.D + qt] = g;
+    }
+}
+
+// rb (the fused launch): the row's whole gz, this half as computed and the other half as
+// this layer's bwd_post launch wrote it (s.gz is not null then)
+template <int K>
+__device__ __forceinline__ void sample_bwd_pre_row(const CouplingArgs &c, const SampleBwdPreArgs &s,
+                                                   const float *gor, int64_t row, float *rb = nullptr) {
+    const int lane = threadIdx.x & 63;
+    const float *zr = s.z + row * c.D;
+    const float gl = s.g_lq ? -s.g_lq[row] : 0.f;  // lq_out = lq_in - (li + ...)
+    constexpr int P = 3 * K + 1;
+    for (int j = lane; j < c.n; j += 64) {
+        const int pi = (int)c.id[j];
+        const int qi = (pi + c.split) % c.D;
+        const float zi = zr[qi];
+        const float v = c.scale * s.out[row * c.D + pi];
+        const float gc = s.g_t[row * 2 * c.n + j] * -sinf(v), gs = s.g_t[row * 2 * c.n + c.n + j] * cosf(v);
+        const float gyi = (gc * c.scale + gs * c.scale) + (gor ? gor[pi] : 0.f);
+        // g_u row: [uw n*K | uh n*K | ud n*(K+1)], the parameters' own layouts back to back
+        float *guw = s.g_u + row * c.n * P + j * K;
+        float *guh = guw + c.n * K;
+        float *gud = s.g_u + row * c.n * P + 2 * c.n * K + j * (K + 1);
+        float g = gyi;
+        if (zi >= -c.bound && zi <= c.bound) {
+            float gw[K], gh[K], gd[K + 1];
+            rqs_point_bwd<K, true>(zi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, gyi, gl, g, gw, gh,
+                                   gd);
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                guw[k] = gw[k];
+                guh[k] = gh[k];
+            }
+#pragma unroll
+            for (int k = 0; k <= K; ++k) gud[k] = gd[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                guw[k] = 0.f;
+                guh[k] = 0.f;
+            }
+#pragma unroll
+            for (int k = 0; k <= K; ++k) gud[k] = 0.f;
+        }
+        if (s.gz) s.gz[row * c.D + qi] = g;
+        if (rb) {
+            const int qt = ((int)c.tr[j] + c.split) % c.D;
+            rb[qi] = g;
+            rb[qt] = s.gz[row * c.D + qt];
+        }
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void coupling_sample_bwd_post_kernel(CouplingArgs c, SampleBwdPostArgs s,
+                                                                       const float *__restrict__ g_out) {
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    if (row < c.rows) sample_bwd_post_row<K>(c, s, g_out ? g_out + row * c.D : nullptr, row);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void coupling_sample_bwd_pre_kernel(CouplingArgs c, SampleBwdPreArgs s,
+                                                                      const float *__restrict__ g_out) {
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    if (row < c.rows) sample_bwd_pre_row<K>(c, s, g_out ? g_out + row * c.D : nullptr, row);
+}
+
+// The backward between two layers of the sampling pass in one launch
+// (fs_coupling_sample_bwd_step): layer l's bwd_pre, whose row of gz (kept in LDS, and written
+// out) is the output gradient of layer l - 1, then layer l - 1's bwd_post on that row, each
+// exactly as the two launches compute it.
+template <int K>
+__global__ __launch_bounds__(256) void coupling_sample_bwd_step_kernel(CouplingArgs c, SampleBwdPreArgs s,
+                                                                       const float *__restrict__ g_out,
+                                                                       CouplingArgs cp, SampleBwdPostArgs sp) {
+    __shared__ float rbuf[kCplRows][kCplMaxDB];
+    float *rb = rbuf[threadIdx.x >> 6];
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    const bool live = row < c.rows;
+    if (live) sample_bwd_pre_row<K>(c, s, g_out ? g_out + row * c.D : nullptr, row, rb);
+    __syncthreads();
+    if (live) sample_bwd_post_row<K>(cp, sp, rb, row);
+}
+
+// ... and their runtime-K twins (see "Separate copies" above): rqs_point_bwd_any<true>, the
+// adjoints that need no rescaling written straight to their rows
+__device__ __forceinline__ void sample_bwd_post_row_any(int K, const CouplingArgs &c, const SampleBwdPostArgs &s,
+                                                        const float *gor, int64_t row) {
+    const int lane = threadIdx.x & 63;
+    const float *zr = s.z + row * c.D;
+    const float gl = s.g_lq ? -s.g_lq[row] : 0.f;
+    const int P = 3 * K + 1;
+    for (int j = lane; j < c.n; j += 64) {
+        const int pt = (int)c.tr[j];
+        const int qt = (pt + c.split) % c.D;
+        const float xt = zr[qt];
+        const float got = gor ? gor[pt] : 0.f;
+        float *gp = s.g_params + (row * c.n + j) * P;
+        float g = got;
+        if (xt >= -c.bound && xt <= c.bound) {
+            const float *p = s.params + (row * c.n + j) * P;
+            float w[kAnyMaxK], h[kAnyMaxK], gw[kAnyMaxK], gh[kAnyMaxK];
+            cond_params_any(K, p, c.sq, w, h);
+            rqs_point_bwd_any<true>(K, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, gp + 2 * K);
+            for (int k = 0; k < K; ++k) {
+                gp[k] = gw[k] / c.sq;
+                gp[K + k] = gh[k] / c.sq;
+            }
+        } else {
+            for (int k = 0; k < P; ++k) gp[k] = 0.f;
+        }
+        if (s.gz) s.gz[row * c.D + qt] = g;
+    }
+}
+
+__device__ __forceinline__ void sample_bwd_pre_row_any(int K, const CouplingArgs &c, const SampleBwdPreArgs &s,
+                                                       const float *gor, int64_t row, float *rb = nullptr) {
+    const int lane = threadIdx.x & 63;
+    const float *zr = s.z + row * c.D;
+    const float gl = s.g_lq ? -s.g_lq[row] : 0.f;
+    const int P = 3 * K + 1;
+    for (int j = lane; j < c.n; j += 64) {
+        const int pi = (int)c.id[j];
+        const int qi = (pi + c.split) % c.D;
+        const float zi = zr[qi];
+        const float v = c.scale * s.out[row * c.D + pi];
+        const float gc = s.g_t[row * 2 * c.n + j] * -sinf(v), gs = s.g_t[row * 2 * c.n + c.n + j] * cosf(v);
+        const float gyi = (gc * c.scale + gs * c.scale) + (gor ? gor[pi] : 0.f);
+        float *guw = s.g_u + row * c.n * P + j * K;
+        float *guh = guw + c.n * K;
+        float *gud = s.g_u + row * c.n * P + 2 * c.n * K + j * (K + 1);
+        float g = gyi;
+        if (zi >= -c.bound && zi <= c.bound) {
+            rqs_point_bwd_any<true>(K, zi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, gyi, gl, g, guw,
+                                    guh, gud);
+        } else {
+            for (int k = 0; k < K; ++k) {
+                guw[k] = 0.f;
+                guh[k] = 0.f;
+            }
+            for (int k = 0; k <= K; ++k) gud[k] = 0.f;
+        }
+        if (s.gz) s.gz[row * c.D + qi] = g;
+        if (rb) {
+            const int qt = ((int)c.tr[j] + c.split) % c.D;
+            rb[qi] = g;
+            rb[qt] = s.gz[row * c.D + qt];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void coupling_sample_bwd_post_any_kernel(int K, CouplingArgs c, SampleBwdPostArgs s,
+                                                                           const float *__restrict__ g_out) {
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    if (row < c.rows) sample_bwd_post_row_any(K, c, s, g_out ? g_out + row * c.D : nullptr, row);
+}
+
+__global__ __launch_bounds__(256) void coupling_sample_bwd_pre_any_kernel(int K, CouplingArgs c, SampleBwdPreArgs s,
+                                                                          const float *__restrict__ g_out) {
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    if (row < c.rows) sample_bwd_pre_row_any(K, c, s, g_out ? g_out + row * c.D : nullptr, row);
+}
+
+__global__ __launch_bounds__(256) void coupling_sample_bwd_step_any_kernel(int K, CouplingArgs c, SampleBwdPreArgs s,
+                                                                           const float *__restrict__ g_out,
+                                                                           CouplingArgs cp, SampleBwdPostArgs sp) {
+    __shared__ float rbuf[kCplRows][kCplMaxDB];
+    float *rb = rbuf[threadIdx.x >> 6];
+    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
+    const bool live = row < c.rows;
+    if (live) sample_bwd_pre_row_any(K, c, s, g_out ? g_out + row * c.D : nullptr, row, rb);
+    __syncthreads();
+    if (live) sample_bwd_post_row_any(K, cp, sp, rb, row);
+}
+
 }  // namespace fs
 
 using namespace fs;
@@ -1937,6 +2167,34 @@ hipError_t fs_coupling_sample_post_impl(const fs_coupling *cp, const float *para
                                         hipStream_t st) {
     const SamplePostArgs s{params, lad_u, lq_in, out, lq_out, nan_flag};
     FS_COUPLING_LAUNCH(coupling_sample_post, s)
+}
+
+hipError_t fs_coupling_sample_bwd_post_impl(const fs_coupling *cp, const float *z, const float *params,
+                                            const float *g_out, const float *g_lq, float *gz, float *g_params,
+                                            hipStream_t st) {
+    const SampleBwdPostArgs s{z, params, g_lq, gz, g_params};
+    FS_COUPLING_LAUNCH(coupling_sample_bwd_post, s, g_out)
+}
+
+hipError_t fs_coupling_sample_bwd_pre_impl(const fs_coupling *cp, const float *z, const float *out, const float *uw,
+                                           const float *uh, const float *ud, const float *g_t, const float *g_out,
+                                           const float *g_lq, float *gz, float *g_u, hipStream_t st) {
+    const SampleBwdPreArgs s{z, out, uw, uh, ud, g_t, g_lq, gz, g_u};
+    FS_COUPLING_LAUNCH(coupling_sample_bwd_pre, s, g_out)
+}
+
+// cp: layer l (bwd_pre), pp: layer l - 1 (bwd_post on the row of gz)
+hipError_t fs_coupling_sample_bwd_step_impl(const fs_coupling *cp, const float *z, const float *out, const float *uw,
+                                            const float *uh, const float *ud, const float *g_t, const float *g_out,
+                                            const float *g_lq, float *gz, float *g_u, const fs_coupling *pp,
+                                            const float *z_prev, const float *params_prev, const float *g_lq_prev,
+                                            float *gz_prev, float *g_params_prev, hipStream_t st) {
+    const fs::CouplingArgs ap = coupling_args(pp);
+    if (ap.rows != cp->rows || ap.D != cp->D || ap.D > kCplMaxDB || pp->K != cp->K || !pp->any_k != !cp->any_k || !gz)
+        return hipErrorInvalidValue;
+    const SampleBwdPreArgs s{z, out, uw, uh, ud, g_t, g_lq, gz, g_u};
+    const SampleBwdPostArgs sp{z_prev, params_prev, g_lq_prev, gz_prev, g_params_prev};
+    FS_COUPLING_LAUNCH(coupling_sample_bwd_step, s, g_out, ap, sp)
 }
 #undef FS_COUPLING_LAUNCH
 

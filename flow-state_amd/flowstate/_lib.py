@@ -164,6 +164,11 @@ _SIGS = {
     "fs_set_lean_gemm": (ctypes.c_int32, [ctypes.c_int32]),
     "fs_kld_loss": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P]),
     "fs_kld_loss_backward": (ctypes.c_int, [_P, _I64, _P, _P]),
+    "fs_kld_loss_mix": (ctypes.c_int, [_P, _I64, _P, _P, _I64, ctypes.c_double, _P, _P, _P, _P]),
+    "fs_kld_loss_mix_backward": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_double, _P, _P, _P, _P]),
+    "fs_coupling_sample_bwd_post": (ctypes.c_int, [_CP] + [_P] * 7),
+    "fs_coupling_sample_bwd_pre": (ctypes.c_int, [_CP] + [_P] * 11),
+    "fs_coupling_sample_bwd_step": (ctypes.c_int, [_CP] + [_P] * 10 + [_CP] + [_P] * 6),
     "fs_linear_f32_pair_bn_sk": (ctypes.c_int, [ctypes.POINTER(GemmF32), ctypes.POINTER(GemmF32),
                                                  ctypes.POINTER(BnFold), ctypes.POINTER(BnFold), ctypes.c_int32, _I64,
                                                  ctypes.c_int32, _I64, _P]),

@@ -164,6 +164,61 @@ def kld_loss(log_q, energy, lq_rev):
     return -torch.mean(log_q) + 0.0 * (torch.mean(energy) + torch.mean(lq_rev))
 
 
+class _KldLossMix(torch.autograd.Function):
+    """loss = ALPHA * (-mean(log_q)) + (1 - ALPHA) * (mean(energy) + mean(lq_rev))
+    (main_algorithm_2.py:316-318) at any ALPHA in one launch each way (fs_kld_loss_mix /
+    fs_kld_loss_mix_backward), _KldLoss's reduction and NaN word handling; the gradients are
+    torch's products -(g ALPHA) * (1 / B) and (g (1 - ALPHA)) * (1 / R), bit for bit."""
+
+    @staticmethod
+    def forward(ctx, log_q, energy, lq_rev, alpha):
+        global _sticky_flag_out
+        from .. import _lib
+
+        loss = torch.empty((), device=log_q.device)
+        word = _sticky_nan if _flags_in_sticky else None
+        if word is not None:
+            _sticky_flag_out = torch.empty((), dtype=torch.bool, device=log_q.device)
+        _lib.check(_lib.load().fs_kld_loss_mix(_lib.ptr(log_q), log_q.shape[0], _lib.ptr(energy), _lib.ptr(lq_rev),
+                                               lq_rev.shape[0], float(alpha), _lib.ptr(word), _lib.ptr(loss),
+                                               _lib.ptr(_sticky_flag_out if word is not None else None),
+                                               _lib.stream_ptr()), "fs_kld_loss_mix")
+        ctx.B, ctx.R, ctx.alpha = log_q.shape[0], lq_rev.shape[0], float(alpha)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from .. import _lib
+
+        g = g.detach().contiguous()
+        gq = torch.empty(ctx.B, device=g.device) if ctx.needs_input_grad[0] else None
+        ge = torch.empty(ctx.R, device=g.device) if ctx.needs_input_grad[1] else None
+        gl = torch.empty(ctx.R, device=g.device) if ctx.needs_input_grad[2] else None
+        _lib.check(_lib.load().fs_kld_loss_mix_backward(_lib.ptr(g), ctx.B, ctx.R, ctx.alpha, _lib.ptr(gq), _lib.ptr(ge),
+                                                        _lib.ptr(gl), _lib.stream_ptr()), "fs_kld_loss_mix_backward")
+        return gq, ge, gl, None
+
+
+def kld_loss_mix(log_q, energy, lq_rev, alpha):
+    """The training loss at ALPHA < 1 from forward_kld's log q and reverse_kld's energies and
+    log q (_KldLossMix) for float32 device vectors; the torch expression of step_loss
+    otherwise."""
+    ok = all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()
+             for t in (log_q, energy, lq_rev)) and log_q.shape[0] >= 1 and energy.shape == lq_rev.shape \
+        and energy.shape[0] >= 1
+    if ok:
+        from .. import _lib
+
+        with _lib.on_device(log_q):
+            return _KldLossMix.apply(log_q, energy, lq_rev, float(alpha))
+    sample_loss = -torch.mean(log_q)
+    energy_loss = torch.mean(energy) + torch.mean(lq_rev)
+    if alpha == 0.0:
+        return 0.0 * sample_loss + energy_loss
+    return alpha * sample_loss + (1 - alpha) * energy_loss
+
+
 def check_nan_flags():
     """Raise the reference's discriminant error if any inverse spline of the pass hit
     a NaN (one device->host read per pass instead of one per layer)."""
@@ -1292,6 +1347,248 @@ def sample_step(layer, z, log_q, nan_flag):
     _lib.check(L.fs_coupling_sample_post(ctypes.byref(c), _lib.ptr(params), _lib.ptr(lad_u), _lib.ptr(log_q),
                                          _lib.ptr(out), _lib.ptr(lq), _lib.ptr(nan_flag), _lib.stream_ptr()),
                "fs_coupling_sample_post")
+    return out, lq
+
+
+# ---------------------------------------------------------------------------
+# The sampling direction with gradients (reverse_kld's term of the loss at ALPHA < 1,
+# main_algorithm_2.py:316-318; Coupling.inverse, coupling.py:104-134): sample_step's two
+# launches as autograd Functions around the conditioner, their adjoints on
+# fs_coupling_sample_bwd_post / _pre (csrc/spline_autograd.hip).  Autograd runs
+# _SamplePost.backward, the conditioner's backward, then _SamplePre.backward; the input
+# gradient gz is one buffer that the two kernels fill half each, handed from the first to the
+# second through the layer's _SampleLink.
+
+# the fused sampling-pass backward is on (FS_FUSED_SAMPLE_GRAD=0: the per-op coupling_sample)
+_fused_sample_grad = os.environ.get("FS_FUSED_SAMPLE_GRAD", "1") != "0"
+# test hook: layer l's bwd_pre and layer l - 1's bwd_post in one launch (fs_coupling_sample_bwd_step)
+_sample_bwd_step = True
+sample_grad_steps = 0  # layers that took sample_step_grad
+sample_bwd_steps = 0  # fs_coupling_sample_bwd_step launches
+# bwd_pre launches left to the previous layer's _SamplePost.backward:
+# {gz's data_ptr: (layer, z, out, uw, uh, ud, g_t, g_out, g_lq, gz, gu, gs)}; each entry holds
+# its gz, so no other tensor can take its address meanwhile
+_pending_sample_bwd = {}
+
+
+class _SampleLink:
+    """What one layer's _SamplePre and _SamplePost share outside autograd: the layer input z
+    and the output buffer (post works in place on it), and in the backward the input
+    gradient gz (post's half written) and g_lq on their way from post to pre."""
+
+    __slots__ = ("z", "out", "need_gz", "gz", "g_lq")
+
+    def __init__(self):
+        self.z = self.out = self.gz = self.g_lq = None
+        self.need_gz = False
+
+
+def _launch_sample_bwd_pre(q):
+    """fs_coupling_sample_bwd_pre of a (pending) entry and the row sum of its per-row
+    unconditional adjoints (as _DensitySplines.backward)."""
+    from .. import _lib
+
+    L, p = _lib.load(), _lib.ptr
+    layer, z, out, uw, uh, ud, g_t, g_out, g_lq, gz, gu, gs = q
+    c = _coupling_desc(layer, z.shape[0])
+    _lib.check(L.fs_coupling_sample_bwd_pre(ctypes.byref(c), p(z), p(out), p(uw), p(uh), p(ud), p(g_t), p(g_out),
+                                            p(g_lq), p(gz), p(gu), _lib.stream_ptr()), "fs_coupling_sample_bwd_pre")
+    _sample_u_rowsum(gu, gs)
+
+
+def _sample_u_rowsum(gu, gs):
+    from .. import _lib
+
+    rows, P = gu.shape
+    _lib.check(_lib.load().fs_linear_f32(P, 0, rows, _lib.ptr(gu), 1, P, None, 0, 0, None, None, 0, None, 0,
+                                         _lib.ptr(gs), _lib.stream_ptr()), "fs_linear_f32")
+
+
+def flush_sample_bwd():
+    """Launch every bwd_pre still pending on its own (none after a complete backward)."""
+    while _pending_sample_bwd:
+        _, q = _pending_sample_bwd.popitem()
+        _launch_sample_bwd_pre(q)
+
+
+class _SampleUParams(torch.autograd.Function):
+    """The unconditional spline parameters of one layer on their way into _SamplePre, created
+    before the pass's first layer: autograd runs the later-created nodes first, so this
+    backward comes after the previous layer's _SamplePost.backward has carried the layer's
+    pending bwd_pre launch (the parameter gradients are views of a buffer that launch's row
+    sum writes).  Whatever is still pending when it runs is launched here, so the gradients
+    it returns are written whichever order the engine took."""
+
+    @staticmethod
+    def forward(ctx, uw, uh, ud):
+        return uw.view_as(uw), uh.view_as(uh), ud.view_as(ud)
+
+    @staticmethod
+    def backward(ctx, guw, guh, gud):
+        flush_sample_bwd()
+        return guw, guh, gud
+
+
+def sample_u_params(flows):
+    """{id(layer): its unconditional parameters through _SampleUParams} for sample_step_grad's
+    u, taken before the first layer of a sampling pass."""
+    _pending_sample_bwd.clear()  # (an interrupted backward's; their buffers are unreachable)
+    held = {}
+    for f in flows:
+        u = f.prqct.unconditional_transform
+        held[id(f)] = _SampleUParams.apply(u.unnormalized_widths, u.unnormalized_heights,
+                                           u.unnormalized_derivatives)
+    return held
+
+
+class _SamplePre(torch.autograd.Function):
+    """fs_coupling_sample_pre: z, uw, uh, ud -> t, out (identity half done, transform half
+    copied), lad_u; backward fs_coupling_sample_bwd_pre."""
+
+    @staticmethod
+    def forward(ctx, z, uw, uh, ud, layer, nan_flag, link, held):
+        from .. import _lib
+
+        # z is the previous layer's output: the backward may leave its launch to that
+        # layer's _SamplePost.backward (fs_coupling_sample_bwd_step)
+        ctx.defer = (held and ctx.needs_input_grad[0] and type(z.grad_fn).__name__ == "_SamplePostBackward"
+                     and not z.retains_grad and not getattr(z, "_backward_hooks", None))
+        z = z.contiguous()
+        uw, uh, ud = uw.contiguous(), uh.contiguous(), ud.contiguous()
+        rows = z.shape[0]
+        _check_shapes(layer, rows, None, uw, uh, ud)
+        t = torch.empty_like(z)
+        out = torch.empty_like(z)
+        lad_u = torch.empty((rows,), dtype=torch.float32, device=z.device)
+        c = _coupling_desc(layer, rows)
+        _lib.require_device(z, uw, nan_flag)
+        _lib.check(_lib.load().fs_coupling_sample_pre(ctypes.byref(c), _lib.ptr(z), _lib.ptr(uw), _lib.ptr(uh),
+                                                      _lib.ptr(ud), _lib.ptr(t), _lib.ptr(out), _lib.ptr(lad_u),
+                                                      _lib.ptr(nan_flag), _lib.stream_ptr()),
+                   "fs_coupling_sample_pre")
+        ctx.save_for_backward(z, uw, uh, ud)
+        ctx.layer, ctx.link = layer, link
+        link.z, link.out, link.need_gz = z, out.detach(), ctx.needs_input_grad[0]
+        ctx.mark_non_differentiable(lad_u)  # its adjoint is -g_lq, handed over by the link
+        ctx.set_materialize_grads(False)
+        return t, out, lad_u
+
+    @staticmethod
+    def backward(ctx, g_t, g_out, g_lad_u):
+        z, uw, uh, ud = ctx.saved_tensors
+        link, layer = ctx.link, ctx.layer
+        if g_t is None and g_out is None and link.g_lq is None:
+            return (None,) * 8
+        K, n, rows = layer.num_bins, z.shape[1] // 2, z.shape[0]
+        P = n * (3 * K + 1)
+        g_t = g_t.contiguous() if g_t is not None else torch.zeros_like(z)
+        g_out = g_out.contiguous() if g_out is not None else None
+        gz = link.gz if link.need_gz else None
+        if link.need_gz and gz is None:  # post's backward did not run: nothing reached its half
+            gz = torch.zeros_like(z)
+        gu = torch.empty((rows, P), dtype=torch.float32, device=z.device)
+        gs = torch.empty((P,), dtype=torch.float32, device=z.device)  # [uw | uh | ud] gradients, one row sum
+        q = (layer, z, link.out, uw, uh, ud, g_t, g_out, link.g_lq, gz, gu, gs)
+        link.gz = link.g_lq = None
+        if ctx.defer and _sample_bwd_step and gz is not None:
+            _pending_sample_bwd[gz.data_ptr()] = q
+        else:
+            _launch_sample_bwd_pre(q)
+        guw = gs[:n * K].view(n, K)
+        guh = gs[n * K:2 * n * K].view(n, K)
+        gud = gs[2 * n * K:].view(n, K + 1)
+        return gz, guw, guh, gud, None, None, None, None
+
+
+class _SamplePost(torch.autograd.Function):
+    """fs_coupling_sample_post: the transform half of out through the conditional inverse
+    spline in place, lq = lq_in - (lad_u + its log-det sum); backward
+    fs_coupling_sample_bwd_post, or with the next layer's bwd_pre pending on this layer's
+    output gradient, both in one launch (fs_coupling_sample_bwd_step)."""
+
+    @staticmethod
+    def forward(ctx, out, params, lad_u, lq_in, layer, nan_flag, link):
+        from .. import _lib
+
+        params = params.contiguous()
+        rows, n, K = out.shape[0], out.shape[1] // 2, layer.num_bins
+        if tuple(params.shape) != (rows, n * (3 * K + 1)) or params.dtype != torch.float32:
+            raise ValueError(f"coupling operand of shape {tuple(params.shape)} / {params.dtype}, expected "
+                             f"{(rows, n * (3 * K + 1))} float32")
+        if lq_in is not None and tuple(lq_in.shape) != (rows,):
+            raise ValueError("log_q must be [rows]")
+        lq = torch.empty((rows,), dtype=torch.float32, device=out.device)
+        c = _coupling_desc(layer, rows)
+        _lib.require_device(out, params, lad_u, lq_in, nan_flag)
+        _lib.check(_lib.load().fs_coupling_sample_post(ctypes.byref(c), _lib.ptr(params), _lib.ptr(lad_u),
+                                                       _lib.ptr(lq_in), _lib.ptr(out), _lib.ptr(lq),
+                                                       _lib.ptr(nan_flag), _lib.stream_ptr()),
+                   "fs_coupling_sample_post")
+        ctx.mark_dirty(out)
+        ctx.save_for_backward(params)
+        ctx.layer, ctx.link = layer, link
+        ctx.has_lq = lq_in is not None
+        ctx.set_materialize_grads(False)
+        return out, lq
+
+    @staticmethod
+    def backward(ctx, g_out, g_lq):
+        global sample_bwd_steps
+        from .. import _lib
+
+        (params,) = ctx.saved_tensors
+        link, layer = ctx.link, ctx.layer
+        if g_out is None and g_lq is None:
+            return (None,) * 7
+        L, p = _lib.load(), _lib.ptr
+        z = link.z
+        g_out = g_out.contiguous() if g_out is not None else None
+        g_lq = g_lq.contiguous() if g_lq is not None else None
+        gz = torch.empty_like(z) if link.need_gz else None
+        gp = torch.empty_like(params)
+        c = _coupling_desc(layer, z.shape[0])
+        q = _pending_sample_bwd.pop(g_out.data_ptr(), None) if g_out is not None else None
+        flush_sample_bwd()  # (not this layer's: on their own)
+        fused = False
+        if q is not None:
+            layer_q, zq, outq, uw, uh, ud, g_t, g_outq, g_lqq, gzq, gu, gs = q
+            cq = _coupling_desc(layer_q, zq.shape[0])
+            # one layer shape and D <= 256 (the row of gz in LDS), else the separate launches
+            fused = (gzq.shape == g_out.shape and zq.shape == z.shape and (cq.K, cq.any_k) == (c.K, c.any_k)
+                     and c.D <= 256)
+            if fused:
+                _lib.check(L.fs_coupling_sample_bwd_step(ctypes.byref(cq), p(zq), p(outq), p(uw), p(uh), p(ud),
+                                                         p(g_t), p(g_outq), p(g_lqq), p(gzq), p(gu), ctypes.byref(c),
+                                                         p(z), p(params), p(g_lq), p(gz), p(gp), _lib.stream_ptr()),
+                           "fs_coupling_sample_bwd_step")
+                _sample_u_rowsum(gu, gs)
+                sample_bwd_steps += 1
+            else:
+                _launch_sample_bwd_pre(q)
+        if not fused:
+            _lib.check(L.fs_coupling_sample_bwd_post(ctypes.byref(c), p(z), p(params), p(g_out), p(g_lq), p(gz), p(gp),
+                                                     _lib.stream_ptr()), "fs_coupling_sample_bwd_post")
+        link.gz, link.g_lq = gz, g_lq
+        return g_out, gp, None, (g_lq if ctx.has_lq else None), None, None, None
+
+
+def sample_step_grad(layer, z, log_q, nan_flag, u=None):
+    """sample_step with autograd: (z, log_q - log_det), differentiable in z, log_q and the
+    layer's parameters; the forward values are sample_step's bit for bit.  u: the layer's
+    unconditional parameters from sample_u_params (then the backward may share a launch with
+    the previous layer's); None takes them from the layer."""
+    global sample_grad_steps
+    p = layer.prqct
+    if u is None:
+        un = p.unconditional_transform
+        uw, uh, ud = un.unnormalized_widths, un.unnormalized_heights, un.unnormalized_derivatives
+    else:
+        uw, uh, ud = u
+    link = _SampleLink()
+    t, out, lad_u = _SamplePre.apply(z, uw, uh, ud, layer, nan_flag, link, u is not None)
+    params = conditioner_from_features(p.transform_net, t)
+    out, lq = _SamplePost.apply(out, params, lad_u, log_q, layer, nan_flag, link)
+    sample_grad_steps += 1
     return out, lq
 
 

@@ -343,6 +343,10 @@ class NormalizingFlow(nn.Module):
     def forward_kld(self, x):
         """core.py:88-103 (fork: no base term): -mean of the summed density-direction
         log-dets, differentiable, BatchNorm in the module's current mode."""
+        return -torch.mean(self._forward_log_q(x))
+
+    def _forward_log_q(self, x):
+        """forward_kld's per-row log q (the summed density-direction log-dets)."""
         from . import autograd_flow as AF
 
         log_q = None  # zeros (core.py:96); the first fused layer starts from 0
@@ -359,7 +363,7 @@ class NormalizingFlow(nn.Module):
         AF.check_nan_flags()
         if log_q is None:
             log_q = torch.zeros(len(x), device=x.device)
-        return -torch.mean(log_q)
+        return log_q
 
     def reverse_kld(self, num_samples=1, beta=1.0, score_fn=True):
         """core.py:105-142 (fork): base draws -> sampling direction -> mean(target
@@ -367,18 +371,28 @@ class NormalizingFlow(nn.Module):
         z = self.q0(num_samples).to(next(self.parameters()).device)
         return self._reverse_kld_from(z, score_fn)
 
-    def _reverse_kld_from(self, z, score_fn=True):
+    def _reverse_kld_from(self, z, score_fn=True, reduce=True):
+        """reduce=False: (per-row target energy, per-row log q, samples) in place of the loss."""
         from . import autograd_flow as AF
 
         log_q = None  # zeros (core.py:118); the first fused layer starts from 0
         grads = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        # with gradients: the fused layers' autograd twins (AF.sample_step_grad), unless
+        # switched off (then the per-op path below)
+        fused = (not grads) or AF._fused_sample_grad
+        held = None  # the layers' unconditional parameters, taken before the first fused layer
         nan_flag = None
         with _lib.on_device(z):
             for flow in self.flows:
-                if not grads and AF.fused_coupling_ok(flow, z):
+                if fused and AF.fused_coupling_ok(flow, z):
                     if nan_flag is None:
                         nan_flag = torch.zeros(1, dtype=torch.int32, device=z.device)
-                    z, log_q = AF.sample_step(flow, z, log_q, nan_flag)
+                    if grads:
+                        if held is None:
+                            held = AF.sample_u_params(self.flows)
+                        z, log_q = AF.sample_step_grad(flow, z, log_q, nan_flag, held[id(flow)])
+                    else:
+                        z, log_q = AF.sample_step(flow, z, log_q, nan_flag)
                 else:
                     if log_q is None:
                         log_q = torch.zeros(len(z), device=z.device)
@@ -402,6 +416,8 @@ class NormalizingFlow(nn.Module):
                 p.requires_grad_(r)
         AF.check_nan_flags()
         energy = self.p._energy(z)
+        if not reduce:
+            return energy, log_q, z
         return torch.mean(energy) + torch.mean(log_q), z
 
     def save(self, path):

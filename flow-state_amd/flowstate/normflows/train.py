@@ -48,7 +48,8 @@ def step_loss(model, x, n_reverse, alpha, flat_bn=None):
     forward term when ALPHA = 0.  With ALPHA = 1 and the model's BatchNorm buffers flat
     (flat_bn, autograd_flow.FlatBatchNorm) the two passes share their launches
     (autograd_flow.paired_kld): same values, same running statistics, half the launches
-    of the forward half of the step."""
+    of the forward half of the step.  With ALPHA < 1 the sampling pass is differentiated on
+    the fused coupling kernels and the loss is one launch (below)."""
     if alpha == 1.0:
         if flat_bn is not None:
             dev = next(model.parameters()).device
@@ -64,14 +65,26 @@ def step_loss(model, x, n_reverse, alpha, flat_bn=None):
         with torch.no_grad():
             energy_loss, _ = model.reverse_kld(n_reverse)
         return model.forward_kld(x) + 0.0 * energy_loss
-    if alpha == 0.0:
+    # ALPHA < 1: the sampling pass is differentiable (autograd_flow.sample_step_grad on the
+    # fused layers); the per-row terms go to one loss launch (autograd_flow.kld_loss_mix:
+    # fs_kld_loss_mix on device float32 vectors, the torch expression otherwise).  With
+    # AF._fused_sample_grad off the step is the per-op one throughout, loss head included.
+    if not AF._fused_sample_grad:
         energy_loss, _ = model.reverse_kld(n_reverse)
+        if alpha == 0.0:
+            with torch.no_grad():
+                sample_loss = model.forward_kld(x)
+            return 0.0 * sample_loss + energy_loss
+        sample_loss = model.forward_kld(x)
+        return alpha * sample_loss + (1 - alpha) * energy_loss
+    z = model.q0(n_reverse).to(next(model.parameters()).device)  # reverse_kld's base draws
+    energy, lq_rev, _ = model._reverse_kld_from(z, reduce=False)
+    if alpha == 0.0:
         with torch.no_grad():
-            sample_loss = model.forward_kld(x)
-        return 0.0 * sample_loss + energy_loss
-    energy_loss, _ = model.reverse_kld(n_reverse)
-    sample_loss = model.forward_kld(x)
-    return alpha * sample_loss + (1 - alpha) * energy_loss
+            log_q = model._forward_log_q(x)
+    else:
+        log_q = model._forward_log_q(x)
+    return AF.kld_loss_mix(log_q, energy, lq_rev, alpha)
 
 
 class _Captured:

@@ -362,6 +362,19 @@ int fs_kld_loss(const float *log_q, int64_t B, const float *energy, const float 
 /* Its gradient: grad_log_q [B] = -grad_loss[0] / B. */
 int fs_kld_loss_backward(const float *grad_loss, int64_t B, float *grad_log_q, void *stream);
 
+/* The Algorithm-2 loss at any ALPHA (main_algorithm_2.py:316-318; NF/normflows/core.py:88-103
+ * forward_kld, core.py:105-142 reverse_kld): loss [1] = alpha * (-mean(log_q [B])) +
+ * (1 - alpha) * (mean(energy [R]) + mean(lq_rev [R])), alpha and 1 - alpha rounded to
+ * float32 as torch rounds python floats.  fs_kld_loss's reduction, nan_word and nan_out. */
+int fs_kld_loss_mix(const float *log_q, int64_t B, const float *energy, const float *lq_rev, int64_t R, double alpha,
+                    const int32_t *nan_word, float *loss, uint8_t *nan_out, void *stream);
+
+/* Its gradients (each nullable; reverse_kld's two terms, core.py:105-142): grad_log_q [B] =
+ * -(grad_loss[0] alpha) / B, grad_energy [R] = grad_lq_rev [R] = (grad_loss[0] (1 - alpha)) / R,
+ * torch's products bit for bit. */
+int fs_kld_loss_mix_backward(const float *grad_loss, int64_t B, int64_t R, double alpha, float *grad_log_q,
+                             float *grad_energy, float *grad_lq_rev, void *stream);
+
 /* unconstrained_rational_quadratic_spline, circular tails (NF/normflows/utils/
  * splines.py:16-222) for M independent elements: x [M], unnormalised widths /
  * heights uw, uh [M][K], derivatives ud [M][K+1] (row-major, contiguous).
@@ -579,7 +592,8 @@ int fs_coupling_density_bwd(const fs_coupling *c, const float *x, const float *p
  * instead of by autograd). */
 int fs_coupling_features_bwd(const fs_coupling *c, const float *x, const float *g_t, float *gx,
                              const float *gx_add, void *stream);
-/* Sampling direction, forward only, in two launches around the conditioner:
+/* Sampling direction, forward (its adjoints: fs_coupling_sample_bwd_* below), in two launches
+ * around the conditioner:
  * pre: t, out (identity half through the inverse unconditional spline, transform half
  * copied), lad_u [rows]; post: the transform half through the inverse conditional spline
  * (in place in out), lq_out = lq_in - (lad_u + its log-det sum).  nan_flag (nullable)
@@ -607,6 +621,34 @@ int fs_coupling_pair_post(const fs_coupling *s, const float *params, const float
 int fs_coupling_bwd_step(const fs_coupling *f, const float *x_f, const float *g_t, float *gx_f, const float *gx_add,
                          const fs_coupling *c, const float *x, const float *params, const float *uw, const float *uh,
                          const float *ud, const float *g_lq, float *gx, float *g_params, float *g_u, void *stream);
+
+/* Adjoints of the sampling direction (Coupling.inverse, coupling.py:104-134; reverse_kld,
+ * core.py:105-142) in two launches around the conditioner's backward, from the layer input z,
+ * g_out [rows][D] and g_lq [rows] (both nullable = 0).  With zi = z[(id_j + split) % D],
+ * yi = uinv(zi), xt = z[(tr_j + split) % D], yt = cinv(xt; params), split = D / 2:
+ * bwd_post (before the conditioner's backward): gz at the (tr_j + split) % D positions and
+ * g_params [rows][D/2][3K+1] through the conditional inverse spline (outside the tails
+ * gz = g_out, g_params = 0);
+ * bwd_pre (after it; out = the layer's output, g_t [rows][D] = the adjoint of t): gz at the
+ * (id_j + split) % D positions through the features and the unconditional inverse spline, and
+ * g_u [rows][(D/2)(3K+1)] = the per-row adjoints of uw, uh, ud back to back as
+ * fs_coupling_density_bwd writes them.  The two write disjoint halves of gz (nullable: the
+ * input needs no gradient).  No allocation, host synchronisation or atomics. */
+int fs_coupling_sample_bwd_post(const fs_coupling *c, const float *z, const float *params, const float *g_out,
+                                const float *g_lq, float *gz, float *g_params, void *stream);
+int fs_coupling_sample_bwd_pre(const fs_coupling *c, const float *z, const float *out, const float *uw,
+                               const float *uh, const float *ud, const float *g_t, const float *g_out,
+                               const float *g_lq, float *gz, float *g_u, void *stream);
+
+/* fs_coupling_sample_bwd_pre of layer c (coupling.py:104-134 / core.py:105-142; gz already
+ * holds its bwd_post half) and fs_coupling_sample_bwd_post of the layer before it (prev, whose
+ * g_out is that gz; gz_prev nullable) in one launch, each row exactly as the two launches
+ * compute it.  Same rows, D, K and any_k on both; D <= 256. */
+int fs_coupling_sample_bwd_step(const fs_coupling *c, const float *z, const float *out, const float *uw,
+                                const float *uh, const float *ud, const float *g_t, const float *g_out,
+                                const float *g_lq, float *gz, float *g_u, const fs_coupling *prev, const float *z_prev,
+                                const float *params_prev, const float *g_lq_prev, float *gz_prev, float *g_params_prev,
+                                void *stream);
 
 /* fs_coupling_pair_post of layers (s, d) and fs_coupling_pair_pre of the next layers
  * (s_next, d_next: the sampling pass's next layer reads z = out, the density pass's next
