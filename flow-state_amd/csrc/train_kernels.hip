@@ -99,6 +99,8 @@ struct GemmLds {
 
 constexpr int kBnMaxK = 256;  // BatchNorm-in-load: widest A (the conditioner's hidden width)
 constexpr int kBnStTiles = 8;  // producer tile statistics loaded per round (batch 256 = one round)
+// registers (f2 pairs) the lean product holds of them: one round, or all of a compile-time tile count
+constexpr int lin_st_regs(int tiles) { return tiles > kBnStTiles ? tiles : kBnStTiles; }
 // k-blocks in flight per wave in the forward products (the A2 shapes: K = 128 over 8 waves
 // = 2 k-blocks each, so all of a wave's operand loads go out before the prologue)
 #ifndef FS_GEMM_BN_PF
@@ -418,22 +420,23 @@ __device__ __forceinline__ void lin_bn_first(const LinBn &bn, f2s (&v)[kBnStTile
 // bn_prologue's arithmetic (column k = thread k, Chan's update over the producer's tiles
 // in order, biased variance, invstd; the lead workgroup's outputs and running statistics);
 // v0 / gk / bk: lin_bn_first's loads
-template <int K, bool FULL>
+template <int K, int TILES>
 __device__ __forceinline__ void lin_bn_prologue(const LinBn &bn, int rows, bool lead, BnLds &S,
-                                                const f2s (&v0)[kBnStTiles], float gk, float bk) {
+                                                const f2s (&v0)[lin_st_regs(TILES)], float gk, float bk) {
     typedef float f2 __attribute__((ext_vector_type(2)));
     const int k = threadIdx.x;
     if (k < K) {
         float n = 0.f, mean = 0.f, m2 = 0.f;
-        if constexpr (FULL) {
-            // the full training batch (256 rows, one round of 8 full tiles): the same update
+        if constexpr (TILES > 0) {
+            // the full training batch (256 rows, one round of 8 full tiles; 512 rows, two rounds,
+            // Algorithm 1's pretraining batch): the same update
             // with the tile sizes known, so its divisions fold to constants.  Bit-identical:
             // nb / nn and n nb / nn are correctly rounded quotients either way (the run-time
             // form below is the IEEE division) and chan_update rounds per operation.  0.45 us
             // per launch in a dependent chain (tools/probes/block_fuse: 9.45 -> 8.55 us per
             // block; tools/train_lin_chain.py 5.70 -> 5.28 us; profiles/r06/).
 #pragma unroll
-            for (int t = 0; t < kBnStTiles; ++t) chan_update(n, mean, m2, v0[t][0], v0[t][1], 32.f);
+            for (int t = 0; t < TILES; ++t) chan_update(n, mean, m2, v0[t][0], v0[t][1], 32.f);
         } else {
             for (int t0 = 0; t0 < bn.tiles; t0 += kBnStTiles) {
                 const int nt = bn.tiles - t0 < kBnStTiles ? bn.tiles - t0 : kBnStTiles;
@@ -470,19 +473,22 @@ __device__ __forceinline__ void lin_bn_prologue(const LinBn &bn, int rows, bool 
     __syncthreads();
 }
 
-// FULL (the full training batch, bn.tiles == kBnStTiles and M == 32 kBnStTiles, uniform per
-// problem): the producer statistics as unconditional buffer loads and the combine's fast
-// path; the same loads and arithmetic, so the same bits (tools/probes/block_fuse's tile
-// form: 4.3 us per BatchNorm-in-load product in a dependent chain).
-template <int K, bool FULL>
-__device__ __forceinline__ void lin_bn_first_t(const LinBn &bn, f2s (&v)[kBnStTiles], float &gk, float &bk) {
-    if constexpr (FULL) {
+// TILES > 0 (the full training batch, bn.tiles == TILES and M == 32 TILES, uniform per
+// problem; TILES = kBnStTiles, Algorithm 2's 256 rows, or 2 kBnStTiles, Algorithm 1's 512:
+// lin_full_tiles): the producer statistics as unconditional buffer loads and the combine's
+// fast path; the same loads and arithmetic, so the same bits (tools/probes/block_fuse's tile
+// form: 4.3 us per BatchNorm-in-load product in a dependent chain).  The two-round form
+// issues both rounds' loads here, ahead of the GEMM operands, and runs the same chan_update
+// sequence in the same tile order as the run-time form's two rounds.
+template <int K, int TILES>
+__device__ __forceinline__ void lin_bn_first_t(const LinBn &bn, f2s (&v)[lin_st_regs(TILES)], float &gk, float &bk) {
+    if constexpr (TILES > 0) {
         const int k = threadIdx.x;
         if (k < K) {
             const __amdgpu_buffer_rsrc_t Sr =
-                __builtin_amdgcn_make_buffer_rsrc((void *)bn.st, (short)0, kBnStTiles * K * 8, 0x00020000);
+                __builtin_amdgcn_make_buffer_rsrc((void *)bn.st, (short)0, TILES * K * 8, 0x00020000);
 #pragma unroll
-            for (int t = 0; t < kBnStTiles; ++t)
+            for (int t = 0; t < TILES; ++t)
                 v[t] = __builtin_bit_cast(f2s, __builtin_amdgcn_raw_buffer_load_b64(Sr, (t * K + k) * 8, 0, 0));
             gk = bn.gamma[k];
             bk = bn.beta[k];
@@ -493,7 +499,7 @@ __device__ __forceinline__ void lin_bn_first_t(const LinBn &bn, f2s (&v)[kBnStTi
 }
 
 // One 32 x 32 tile (bx, by) of P by 8 waves: wave w reduces the k-blocks 8w + 64s
-template <int KBW, bool FULL = false>
+template <int KBW, int TILES = 0>
 __device__ __forceinline__ void lin_tile(const LinP &P, const LinBn &bn, unsigned bx, unsigned by, LinLds &L) {
     constexpr int K = 64 * KBW;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -503,9 +509,9 @@ __device__ __forceinline__ void lin_tile(const LinP &P, const LinBn &bn, unsigne
     const bool aok = m < M;
     const __amdgpu_buffer_rsrc_t Ar = lin_rsrc(P.A, M * K * 4), Wr = lin_rsrc(P.W, P.N * K * 4);
     const int kq = 8 * w + 4 * h;  // this lane's first k in each k-block
-    f2s st0[kBnStTiles];
+    f2s st0[lin_st_regs(TILES)];
     float gk = 0.f, bk = 0.f;
-    if (bn.on) lin_bn_first_t<K, FULL>(bn, st0, gk, bk);
+    if (bn.on) lin_bn_first_t<K, TILES>(bn, st0, gk, bk);
     t4 a[KBW], b[KBW];
 #pragma unroll
     for (int s = 0; s < KBW; ++s) {
@@ -531,7 +537,7 @@ __device__ __forceinline__ void lin_tile(const LinP &P, const LinBn &bn, unsigne
             ep_bias = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(lin_rsrc(P.bias, P.N * 4), col * 4, 0, 0));
     }
     if (bn.on) {
-        lin_bn_prologue<K, FULL>(bn, M, bx == 0 && by == 0, L.S, st0, gk, bk);
+        lin_bn_prologue<K, TILES>(bn, M, bx == 0 && by == 0, L.S, st0, gk, bk);
         const int nt = P.N / 32;
 #pragma unroll
         for (int s = 0; s < KBW; ++s) {
@@ -590,25 +596,32 @@ __device__ __forceinline__ void lin_tile(const LinP &P, const LinBn &bn, unsigne
     }
 }
 
-static bool lin_full(const LinP &P, const LinBn &bn) {
-    return bn.tiles == kBnStTiles && P.M == 32 * kBnStTiles;
+// FS_LIN_FULL16=0 (tools/build_variant.sh): the 512-row batch keeps the run-time form (A/B)
+#ifndef FS_LIN_FULL16
+#define FS_LIN_FULL16 1
+#endif
+// the compile-time tile count of a full training batch (kBnStTiles or 2 kBnStTiles); 0: the run-time form
+static int lin_full_tiles(const LinP &P, const LinBn &bn) {
+    if (bn.tiles == kBnStTiles && P.M == 32 * kBnStTiles) return kBnStTiles;
+    if (FS_LIN_FULL16 && bn.tiles == 2 * kBnStTiles && P.M == 64 * kBnStTiles) return 2 * kBnStTiles;
+    return 0;
 }
 
 // workgroups [0, t0) compute problem 0 (column-major over its mt0 row tiles), the rest
 // problem 1; the branch is uniform, so each workgroup reads only its own problem's arguments
-// FULL: every BatchNorm-in-load problem of the launch is a full training batch (lin_full;
-// the host picks the kernel), so the generic kernel keeps its register budget (74 VGPRs, three
+// TILES > 0: every BatchNorm-in-load problem of the launch is a full training batch of TILES
+// row tiles (lin_full_tiles; the host picks the kernel), so the generic kernel keeps its register budget (74 VGPRs, three
 // workgroups per CU for the final Linear's 1472-workgroup launch) and the hidden layers'
 // BatchNorm-in-load products take the full-batch form
-template <int KBW, bool FULL>
+template <int KBW, int TILES>
 __global__ __launch_bounds__(512) void gemm_lin_kernel(Lin2 a) {
     __shared__ LinLds L;
     const unsigned b = blockIdx.x;
     if (b < a.t0) {
-        lin_tile<KBW, FULL>(a.p[0], a.b[0], b % a.mt0, b / a.mt0, L);
+        lin_tile<KBW, TILES>(a.p[0], a.b[0], b % a.mt0, b / a.mt0, L);
     } else {
         const unsigned c = b - a.t0;
-        lin_tile<KBW, FULL>(a.p[1], a.b[1], c % a.mt1, c / a.mt1, L);
+        lin_tile<KBW, TILES>(a.p[1], a.b[1], c % a.mt1, c / a.mt1, L);
     }
 }
 
@@ -1699,15 +1712,18 @@ static hipError_t lin_launch(const GemmArgs &g0, const BnIn *b0, const GemmArgs 
         a.mt1 = 1;
     }
     const dim3 grid(a.t0 + t1), block(512);
-    // the full-batch kernel when some problem has a BatchNorm-in-load and every one that has
-    // is a full training batch
-    const bool any_bn = a.b[0].on || (g1 && a.b[1].on);
-    const bool full = any_bn && (!a.b[0].on || lin_full(a.p[0], a.b[0])) && (!g1 || !a.b[1].on || lin_full(a.p[1], a.b[1]));
+    // a full-batch kernel when some problem has a BatchNorm-in-load and every one that has
+    // is a full training batch of the same tile count
+    const bool on0 = a.b[0].on, on1 = g1 && a.b[1].on;
+    const int f0 = on0 ? lin_full_tiles(a.p[0], a.b[0]) : 0, f1 = on1 ? lin_full_tiles(a.p[1], a.b[1]) : 0;
+    const int full = (on0 && on1) ? (f0 == f1 ? f0 : 0) : (on0 ? f0 : f1);
 #define FS_LIN_K(KB)                                                                               \
-    if (full)                                                                                      \
-        hipLaunchKernelGGL((gemm_lin_kernel<KB, true>), grid, block, 0, st, a);                    \
+    if (full == kBnStTiles)                                                                        \
+        hipLaunchKernelGGL((gemm_lin_kernel<KB, kBnStTiles>), grid, block, 0, st, a);              \
+    else if (full == 2 * kBnStTiles)                                                               \
+        hipLaunchKernelGGL((gemm_lin_kernel<KB, 2 * kBnStTiles>), grid, block, 0, st, a);          \
     else                                                                                           \
-        hipLaunchKernelGGL((gemm_lin_kernel<KB, false>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((gemm_lin_kernel<KB, 0>), grid, block, 0, st, a);
     switch (g0.K) {
         case 64: FS_LIN_K(1) break;
         case 128: FS_LIN_K(2) break;

@@ -9,6 +9,7 @@ rebuilt from the per-run device results afterwards:
 
   equilibrate        main_algorithm_1.py:202-210  (particle_displacement, adjust_displacement, sample)
   production         main_algorithm_1.py:240-251  (training samples, run-major)
+  pretrain           main_algorithm_1.py:268, 294-331  (forward_kld epochs on them, one Adam; HIP-graph steps)
   testing_phase      main_algorithm_1.py:375-424  (BIG_MOVE_INTERVAL local moves + one nf_big_move per attempt)
   well_statistics    main_algorithm_1.py:443-455 -> utils.py:61-101 (calculate_well_statistics per run)
   free_energy_curve  utils.py:738-763 (plot_avg_free_energy's mean / sem / std, no plotting)
@@ -83,6 +84,132 @@ def production(bmc: BatchedMonteCarlo, steps, sampling_frequency, half_box=None)
     hb = bmc.phys.half_width if half_box is None else float(half_box)
     samples = snap.xy.reshape(-1, bmc.N, 2) - hb
     return snap, samples
+
+
+@dataclass
+class PretrainResult:
+    """Outputs of the pretraining stage (main_algorithm_1.py:294-319)."""
+    loss_hist: np.ndarray                  # every step's float32 loss, in order, as float64 (np.append, :317)
+    loss_epoch: list                       # per epoch: sum of loss.item() / number of batches (:318-319)
+    skipped: int = 0                       # steps whose loss was NaN / inf (:310-311): no backward, no Adam step
+    adam_steps: int = 0                    # Adam's own step count afterwards (the steps that were not skipped)
+    graphed: bool = False                  # the steps were HIP-graph replays (train.GraphedTrainStep)
+    files: dict = field(default_factory=dict)  # {"loss": path, "model": path} when out_dir was given
+
+
+def _index_batches(n, batch_size):
+    """The index batches of DataLoader(TensorDataset(data), batch_size, shuffle=True) for
+    one epoch: the same sampler and the same draws from torch's default generator, the
+    partial last batch kept (Algorithm2._batches' index trick, its dataset and collate)."""
+    from torch.utils.data import DataLoader
+
+    from .algorithm2 import _Indices, _first  # (algorithm2 imports this module: at call time)
+
+    return list(DataLoader(_Indices(n), batch_size=batch_size, shuffle=True, collate_fn=_first))
+
+
+def pretrain(model, samples, epochs=100, batch_size=512, lr=1e-4, weight_decay=0.0, graphed=None, out_dir=None):
+    """main_algorithm_1.py:268, 294-331: the flow's first training round on the production
+    phase's samples, forward_kld only, one Adam for all epochs.
+
+    samples: global_samples_nf as production() returns it, (M, N, 2) or (M, 2N), numpy or
+    tensor, already centred; converted as get_dataloader does (reshape to (M, 2N), float32,
+    the model's device).  Each epoch's batches are those of DataLoader(TensorDataset(data),
+    batch_size, shuffle=True) built once before the loop (_index_batches; the driver's
+    logging also draws one extra iterator at :272 before training: call
+    torch.utils.data.DataLoader the same way first if a whole run is to be replayed draw
+    for draw).  A step whose loss is NaN / inf is skipped (:310-311) and counted; its loss
+    still enters loss_hist and loss_epoch.  A partial last batch of one row raises, as
+    torch's train-mode BatchNorm does in the reference.
+
+    graphed=None: HIP-graph replays of the step on a device model
+    (train.GraphedTrainStep(..., reverse=False), one graph per batch size), the eager loop
+    otherwise.  Per epoch the shuffled set is gathered once and the steps replay back to
+    back; the host reads the losses and the spline NaN flags once per epoch.  A skipped
+    graphed step also puts the BatchNorm running statistics back (the reference's forward
+    has written NaN statistics by then, which its eval-mode passes keep).
+    graphed=False: the reference loop as written, torch.optim.Adam and model.forward_kld,
+    on any device.
+
+    Afterwards the model is in eval mode with its packed image invalidated.  out_dir:
+    loss_function_data.json (plot_loss's data file) and
+    initial_model_circularspline_res_dense.pth (:326-327) are written there."""
+    p0 = next(model.parameters())
+    dev = p0.device
+    data = torch.as_tensor(samples)
+    data = data.reshape(data.shape[0], -1).to(torch.float32).to(dev)
+    M, bs, epochs = int(data.shape[0]), int(batch_size), int(epochs)
+    D = model.flows[0].num_input_channels
+    if data.dim() != 2 or data.shape[1] != D:
+        raise ValueError(f"samples must be (M, {D // 2}, 2) or (M, {D}), got {tuple(torch.as_tensor(samples).shape)}")
+    if M < 1 or bs < 1:
+        raise ValueError("pretrain needs at least one sample and batch_size >= 1")
+    tail = M % bs
+    if tail == 1 or bs == 1:
+        raise ValueError("Expected more than 1 value per channel when training (a last batch of one row)")
+    if graphed is None:
+        graphed = dev.type == "cuda"
+    graphed = bool(graphed)
+    model.train()
+    hist, loss_epoch, skipped = [], [], 0
+    if graphed:
+        from .normflows.train import GraphedTrainStep
+
+        main = min(bs, M)  # fewer samples than one batch: the only batch is the "tail"
+        step = GraphedTrainStep(model, main, lr, weight_decay, example=data[:main], reverse=False,
+                                extra_batch_sizes=(tail,) if (tail and M > bs) else ())
+        for _ in range(epochs):
+            batches = _index_batches(M, bs)
+            step.reset_nan()
+            shuffled = data[torch.cat(batches).to(dev)]
+            losses, flags, off = [], [], 0
+            for b in batches:
+                loss, flag = step.step(shuffled[off:off + b.numel()], check=False)
+                off += b.numel()
+                losses.append(loss.reshape(()))
+                flags.append(flag.reshape(()))
+            vals = torch.stack(losses).cpu()
+            if bool(torch.stack(flags).any()):
+                raise ValueError("Discriminant computation resulted in NaN.")  # splines.py:176-183
+            hist.append(vals.numpy().astype(np.float64))
+            total = 0.0
+            for v in vals.tolist():
+                total += v  # epoch_loss += loss.item(), in batch order
+            loss_epoch.append(total / len(batches))
+            skipped += int((~torch.isfinite(vals)).sum())
+        counts = [st["step"] for st in step.opt.state.values() if "step" in st]
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+        for _ in range(epochs):
+            total = 0.0
+            batches = _index_batches(M, bs)
+            for b in batches:
+                opt.zero_grad()
+                loss = model.forward_kld(data[b.to(dev)])
+                if torch.isnan(loss) or torch.isinf(loss):
+                    skipped += 1
+                else:
+                    loss.backward()
+                    opt.step()
+                hist.append(loss.detach().to("cpu").numpy().astype(np.float64).reshape(1))
+                total += loss.item()
+            loss_epoch.append(total / len(batches))
+        counts = [st["step"] for st in opt.state.values() if "step" in st]
+    model.eval()
+    model.invalidate_packed()
+    res = PretrainResult(np.concatenate(hist) if hist else np.array([]), loss_epoch, skipped,
+                         int(counts[0]) if counts else 0, graphed)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        res.files["loss"] = io.write_loss_history(out_dir, loss_epoch)
+        res.files["model"] = os.path.join(out_dir, "initial_model_circularspline_res_dense.pth")
+        # a graphed step has re-homed the parameters and running statistics as views of a few
+        # flat buffers: written as own tensors, so the file holds each exactly once
+        sd = model.state_dict()
+        for k in sd:
+            sd[k] = sd[k].detach().clone()
+        torch.save(sd, res.files["model"])
+    return res
 
 
 @dataclass

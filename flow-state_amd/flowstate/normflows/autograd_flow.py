@@ -132,7 +132,7 @@ class _KldLoss(torch.autograd.Function):
         if word is not None:
             _sticky_flag_out = torch.empty((), dtype=torch.bool, device=log_q.device)
         _lib.check(_lib.load().fs_kld_loss(_lib.ptr(log_q), log_q.shape[0], _lib.ptr(energy), _lib.ptr(lq_rev),
-                                           lq_rev.shape[0], _lib.ptr(word), _lib.ptr(loss),
+                                           0 if lq_rev is None else lq_rev.shape[0], _lib.ptr(word), _lib.ptr(loss),
                                            _lib.ptr(_sticky_flag_out if word is not None else None),
                                            _lib.stream_ptr()), "fs_kld_loss")
         ctx.B = log_q.shape[0]
@@ -150,9 +150,19 @@ class _KldLoss(torch.autograd.Function):
         return gq, None, None
 
 
-def kld_loss(log_q, energy, lq_rev):
+def kld_loss(log_q, energy=None, lq_rev=None):
     """The ALPHA = 1 training loss from forward_kld's log q and reverse_kld's energies and
-    log q (_KldLoss) for float32 device vectors; the torch expression otherwise."""
+    log q (_KldLoss) for float32 device vectors; the torch expression otherwise.  Without
+    energy and lq_rev (forward-only training, main_algorithm_1.py:307) the loss is
+    forward_kld's -mean(log_q) alone: the same launch with no reverse term."""
+    if energy is None and lq_rev is None:
+        if log_q.is_cuda and log_q.dtype == torch.float32 and log_q.dim() == 1 and log_q.is_contiguous() \
+                and log_q.shape[0] >= 1:
+            from .. import _lib
+
+            with _lib.on_device(log_q):
+                return _KldLoss.apply(log_q, None, None)
+        return -torch.mean(log_q)
     ok = all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()
              for t in (log_q, energy, lq_rev)) and log_q.shape[0] >= 1 and energy.shape == lq_rev.shape \
         and energy.shape[0] >= 1 and not energy.requires_grad and not lq_rev.requires_grad

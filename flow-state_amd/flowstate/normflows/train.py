@@ -31,6 +31,10 @@ torch.cuda.graph (fused spline kernels and HIP GEMMs included) and replays it:
     step.  (The reference stops inside the failing step's sampling pass, after that pass
     has updated the running statistics of the layers up to the failing one; here that
     step's updates are dropped as a whole.)
+
+Algorithm 1's pretraining step (main_algorithm_1.py:303-314) is the same graph without the
+reverse term: GraphedTrainStep(..., reverse=False), loss = forward_kld(batch) alone
+(forward_loss), for a flow without a target.
 """
 import inspect
 
@@ -39,8 +43,20 @@ import torch
 from . import autograd_flow as AF
 
 
-def step_loss(model, x, n_reverse, alpha, flat_bn=None):
-    """loss = ALPHA * forward_kld(x) + (1 - ALPHA) * reverse_kld(n_reverse)
+def forward_loss(model, x):
+    """The Algorithm-1 pretraining loss, model.forward_kld(x) and nothing else
+    (main_algorithm_1.py:307): no base draws, no target energy, no sampling pass, so the
+    model needs no target (p = None).  On float32 device rows the mean and the negation are
+    the one-launch head (autograd_flow.kld_loss without the reverse terms)."""
+    if x.is_cuda and x.dtype == torch.float32:
+        return AF.kld_loss(model._forward_log_q(x))
+    return model.forward_kld(x)
+
+
+def step_loss(model, x, n_reverse, alpha, flat_bn=None, reverse=True):
+    """reverse=False: forward_loss(model, x), the forward-only step of Algorithm 1 (n_reverse,
+    alpha and flat_bn are unused).  Otherwise
+    loss = ALPHA * forward_kld(x) + (1 - ALPHA) * reverse_kld(n_reverse)
     (main_algorithm_2.py:316-318).  With ALPHA = 1 (the reference's setting) the
     reverse term only contributes its value (0 * e: NaN / inf when e is, so the skip
     rule sees it) and its BatchNorm statistics, so it runs without autograd: its
@@ -50,6 +66,8 @@ def step_loss(model, x, n_reverse, alpha, flat_bn=None):
     (autograd_flow.paired_kld): same values, same running statistics, half the launches
     of the forward half of the step.  With ALPHA < 1 the sampling pass is differentiated on
     the fused coupling kernels and the loss is one launch (below)."""
+    if not reverse:
+        return forward_loss(model, x)
     if alpha == 1.0:
         if flat_bn is not None:
             dev = next(model.parameters()).device
@@ -102,11 +120,20 @@ class _Captured:
 
 class GraphedTrainStep:
     def __init__(self, model, batch_size, lr, weight_decay=0.0, alpha=1.0, warmup=3, example=None,
-                 extra_batch_sizes=(), paired=True):
+                 extra_batch_sizes=(), paired=True, reverse=True):
         """Captures the step for `batch_size` (reverse_kld always draws `batch_size`
         samples, as the reference's reverse_kld(BATCH_SIZE)) and for every size in
         extra_batch_sizes (e.g. the epoch's partial last batch); all graphs share the
-        parameters, gradients and one Adam state."""
+        parameters, gradients and one Adam state.
+
+        reverse=False: the forward-only step of Algorithm 1's pretraining
+        (main_algorithm_1.py:303-314): the loss is forward_loss(model, x), so the model
+        needs no target (p = None) and `alpha` / `paired` are unused.  The BatchNorm
+        running statistics are updated inside the forward there, so each graph snapshots
+        them first and puts them back after a step that must leave no trace: one whose
+        loss is not finite (Adam skips it) or one after the sticky spline-NaN word is set.
+        The buffers are re-homed flat (FlatBatchNorm), so that is three copies and three
+        selects per step, not three per BatchNorm module (960 modules at A1 depth)."""
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise ValueError("GraphedTrainStep needs the model on the GPU")
@@ -117,12 +144,13 @@ class GraphedTrainStep:
             model.q0.device = dev
         self.batch_size = int(batch_size)
         self.alpha = float(alpha)
+        self.reverse = bool(reverse)
         self.D = model.flows[0].num_input_channels
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.opt = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay, capturable=True)
         # BatchNorm running buffers re-homed flat: the step's two passes share launches
         # (step_loss, autograd_flow.paired_kld); None keeps them separate
-        self.flat_bn = AF.FlatBatchNorm.try_build(model) if paired else None
+        self.flat_bn = AF.FlatBatchNorm.try_build(model) if (paired or not self.reverse) else None
         # sticky spline-NaN word of the replays since the last reset_nan() (see the module doc)
         self._sticky = torch.zeros(1, dtype=torch.int32, device=dev)
         self._one = torch.ones((), device=dev)  # the captured backward's seed gradient
@@ -182,7 +210,7 @@ class GraphedTrainStep:
                     for b, t in zip(bn_backup, bn_bufs):
                         b.copy_(t)
                 self._zero_grad()
-                loss = step_loss(model, x, self.batch_size, self.alpha, self.flat_bn)
+                loss = step_loss(model, x, self.batch_size, self.alpha, self.flat_bn, self.reverse)
                 loss.backward(self._one)  # a constant seed gradient: no fill launch
                 self._gather_grads()
                 nan_flag, only_sticky = AF.reduce_nan_flags(dev)
@@ -203,6 +231,10 @@ class GraphedTrainStep:
                 if bn_bufs:
                     with torch.no_grad():
                         failed = self._sticky[0] != 0
+                        if not self.reverse:
+                            # forward-only: a skipped step leaves no trace at all (the
+                            # reference's forward has written NaN running statistics by then)
+                            failed = failed | ~torch.isfinite(loss.detach())
                         for b, t in zip(bn_backup, bn_bufs):
                             t.copy_(torch.where(failed, b, t))
         finally:
@@ -358,7 +390,8 @@ class GraphedTrainStep:
 
     def _eager_step(self, x):
         self._zero_grad()
-        loss = step_loss(self.model, x, self.batch_size, self.alpha, self.flat_bn)
+        bn = [(t, t.detach().clone()) for t in self._bn_buffers()] if not self.reverse else ()
+        loss = step_loss(self.model, x, self.batch_size, self.alpha, self.flat_bn, self.reverse)
         if bool(~(torch.isnan(loss) | torch.isinf(loss))):
             loss.backward()
             self._gather_grads()
@@ -366,6 +399,10 @@ class GraphedTrainStep:
                 self._adam_step()
             else:
                 self.opt.step()
+        else:
+            with torch.no_grad():
+                for t, b in bn:  # forward-only: as the graphed step, a skipped step leaves no trace
+                    t.copy_(b)
         return loss.detach()
 
     def step(self, batch, check=True):
