@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "fs_internal.h"
 
@@ -592,6 +593,79 @@ __global__ __launch_bounds__(256) void rqs_backward_any_kernel(int64_t M, int K,
     rqs_point_bwd_any<INV>(K, xv, uw + i * K, uh + i * K, ud + i * (K + 1), B, go, gl, gx[i], pw, ph, pd);
 }
 
+// ---------------------------------------------------------------------------
+// The bin count of the coupling kernels below: Bins<KT> is a compile-time K = KT (5, 8, 15, 32),
+// Bins<0> a run-time one, 1 <= K <= kAnyMaxK (fs_coupling.any_k: the general-shape mode's training
+// step at a bin count no kernel is instantiated for).  Each row function and kernel is written once
+// over it.  What differs between the two lies behind the policy: the spline family underneath (the
+// instantiated one scans registers; the _any one indexes per-thread arrays of kAnyMaxK in private
+// memory and keeps the knot adjoints sparse), the arrays' capacity, the loops' unrolling and where
+// the adjoints are stored (adj_dst).  knots_pair and density_bwd_row4 keep both shapes of one
+// statement sequence behind `if constexpr (B::fixed)`.  All of this is arranged so that every
+// instantiation compiles to the instruction stream it had as a separate copy (DESIGN.md,
+// 'General-shape mode'): same operations in the same order, so each row is what the single-layer
+// entry points give, and at K in {5, 8, 15, 32} Bins<0> gives what Bins<K> gives up to the
+// compiler's choice of instructions.
+template <int KT>
+struct Bins {
+    static constexpr int kt = KT;
+    static constexpr bool fixed = KT > 0;
+    static constexpr int cap = fixed ? KT : kAnyMaxK;  // of an array over the bins
+    static constexpr int unroll = fixed ? KT + 1 : 4;   // whole loop (at most K + 1 trips) / as the _any family
+    using KnotSet = std::conditional_t<fixed, Knots<KT>, KnotsAny>;
+    int rt;  // the run-time K (Bins<0> only)
+    __device__ __forceinline__ int k() const { return fixed ? KT : rt; }
+};
+
+// for (int k = 0; k < n; ++k) { body } in a function templated on the policy B: unrolled whole with a
+// compile-time K (the arrays it indexes stay registers), left to the compiler with a run-time one.
+// A macro, because where a function that took the body is inlined changes the instantiated
+// kernels' instruction streams.
+#define FS_BINS_FOR(k, n, ...)                                              \
+    {                                                                       \
+        if constexpr (B::fixed) {                                           \
+            _Pragma("unroll") for (int k = 0; k < (n); ++k) { __VA_ARGS__ } \
+        } else {                                                            \
+            for (int k = 0; k < (n); ++k) { __VA_ARGS__ }                   \
+        }                                                                   \
+    }
+
+// the spline primitives of either family
+template <class B>
+__device__ __forceinline__ void bins_build_knots(B bins, const float *u, float bound, typename B::KnotSet &kn) {
+    if constexpr (B::fixed)
+        build_knots<B::kt>(u, bound, kn);
+    else
+        build_knots_any(bins.rt, u, bound, kn);
+}
+
+template <bool INV, class B>
+__device__ __forceinline__ void bins_eval_knots(B bins, float xv, const float *wc, const float *hc, const float *dd,
+                                                float &out, float &lad, int32_t *nan_flag) {
+    if constexpr (B::fixed)
+        rqs_eval_knots<B::kt, INV>(xv, wc, hc, dd, out, lad, nan_flag);
+    else
+        rqs_eval_knots_any<INV>(bins.rt, xv, wc, hc, dd, out, lad, nan_flag);
+}
+
+template <bool INV, class B>
+__device__ __forceinline__ void bins_point(B bins, float xv, const float *uw, const float *uh, const float *dd,
+                                           float bound, float &out, float &lad, int32_t *nan_flag) {
+    if constexpr (B::fixed)
+        rqs_point<B::kt, INV>(xv, uw, uh, dd, bound, out, lad, nan_flag);
+    else
+        rqs_point_any<INV>(bins.rt, xv, uw, uh, dd, bound, out, lad, nan_flag);
+}
+
+template <bool INV, class B>
+__device__ __forceinline__ void bins_point_bwd(B bins, float xv, const float *uw, const float *uh, const float *dd,
+                                               float bound, float go, float gl, float &gx, float *guw, float *guh,
+                                               float *gud) {
+    if constexpr (B::fixed)
+        rqs_point_bwd<B::kt, INV>(xv, uw, uh, dd, bound, go, gl, gx, guw, guh, gud);
+    else
+        rqs_point_bwd_any<INV>(bins.rt, xv, uw, uh, dd, bound, go, gl, gx, guw, guh, gud);
+}
 
 // ---------------------------------------------------------------------------
 // One coupling layer of the training path around its conditioner: the feature gather,
@@ -602,6 +676,7 @@ __global__ __launch_bounds__(256) void rqs_backward_any_kernel(int64_t M, int K,
 struct CouplingArgs {
     int64_t rows;
     int D, n, split;
+    int K;  // the bin count, read by the Bins<0> kernels only (in what was padding)
     const int64_t *id, *tr;
     float bound, scale, sq;
 };
@@ -612,9 +687,10 @@ __device__ __forceinline__ float wave_sum(float v) {
     return __shfl(v, 0);
 }
 
-template <int K>
-__device__ __forceinline__ void cond_params(const float *p, float sq, float *w, float *h) {
-#pragma unroll
+template <class B>
+__device__ __forceinline__ void cond_params(B bins, const float *p, float sq, float *w, float *h) {
+    const int K = bins.k();
+#pragma unroll B::unroll
     for (int k = 0; k < K; ++k) {
         w[k] = p[k] / sq;  // params[..., :K] / sqrt(H) (coupling.py:340-342)
         h[k] = p[K + k] / sq;
@@ -634,10 +710,10 @@ struct DensityFwdArgs {
     float *out, *lq_out;
 };
 
-template <int K>
-__device__ __forceinline__ void density_fwd_row(const CouplingArgs &c, const DensityFwdArgs &d, int64_t row,
+template <class B>
+__device__ __forceinline__ void density_fwd_row(B bins, const CouplingArgs &c, const DensityFwdArgs &d, int64_t row,
                                                 float *rb = nullptr) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, K = bins.k();
     const float *xr = d.x + row * c.D;
     float sc = 0.f, su = 0.f;
     for (int j = lane; j < c.n; j += 64) {
@@ -646,13 +722,13 @@ __device__ __forceinline__ void density_fwd_row(const CouplingArgs &c, const Den
         float yt = xt, lt = 0.f;
         if (xt >= -c.bound && xt <= c.bound) {
             const float *p = d.params + (row * c.n + j) * (3 * K + 1);
-            float w[K], h[K];
-            cond_params<K>(p, c.sq, w, h);
-            rqs_point<K, false>(xt, w, h, p + 2 * K, c.bound, yt, lt, nullptr);
+            float w[B::cap], h[B::cap];
+            cond_params(bins, p, c.sq, w, h);
+            bins_point<false>(bins, xt, w, h, p + 2 * K, c.bound, yt, lt, nullptr);
         }
         float yi = xi, li = 0.f;
         if (xi >= -c.bound && xi <= c.bound)
-            rqs_point<K, false>(xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
+            bins_point<false>(bins, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
         d.out[row * c.D + (pt + c.D - c.split) % c.D] = yt;
         d.out[row * c.D + (pi + c.D - c.split) % c.D] = yi;
         if (rb) {  // the row for the next layer's features in the same launch
@@ -667,27 +743,37 @@ __device__ __forceinline__ void density_fwd_row(const CouplingArgs &c, const Den
     if (lane == 0) d.lq_out[row] = (d.lq_in ? d.lq_in[row] : 0.f) + (sc + su);
 }
 
-template <int K>
+// KT: Bins<KT>, with c.K the run-time bin count of Bins<0>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_density_fwd_kernel(CouplingArgs c, DensityFwdArgs d) {
     const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) density_fwd_row<K>(c, d, row);
+    if (row < c.rows) density_fwd_row(Bins<KT>{c.K}, c, d, row);
 }
 
-// its adjoints: gx (both halves, spline part), g_params [rows][n][3K+1], g_u the per-row
-// unconditional adjoints [rows][n][3K+1] (summed over rows by the caller)
+// Where bins_point_bwd's adjoints go.  With a compile-time K they are collected in registers and
+// stored to their rows afterwards; with a run-time K the arrays are private memory anyway, so those
+// that are stored as they are are written straight to their rows (adj_dst) and only the rescaled
+// ones are left to store.
+template <class B>
+__device__ __forceinline__ float *adj_dst(float *reg, float *row) {
+    return B::fixed ? reg : row;
+}
+
+// density_fwd_row's adjoints: gx (both halves, spline part), g_params [rows][n][3K+1], g_u the
+// per-row unconditional adjoints [rows][n][3K+1] (summed over rows by the caller)
 // two waves per row: wave part 0 takes the conditional spline's adjoints, part 1 the
 // unconditional one's (each lane one feature), so the row's work is spread twice as wide.
 // gor: the row of g_out (nullable: no output gradient)
-template <int K>
-__device__ __forceinline__ void density_bwd_row(const CouplingArgs &c, const float *__restrict__ x,
+template <class B>
+__device__ __forceinline__ void density_bwd_row(B bins, const CouplingArgs &c, const float *__restrict__ x,
                                                 const float *__restrict__ params, const float *__restrict__ uw,
                                                 const float *__restrict__ uh, const float *__restrict__ ud,
                                                 const float *gor, const float *__restrict__ g_lq, float *gx,
                                                 float *g_params, float *g_u, int64_t row, int part) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, K = bins.k();
     const float *xr = x + row * c.D;
     const float gl = g_lq ? g_lq[row] : 0.f;
-    constexpr int P = 3 * K + 1;
+    const int P = 3 * K + 1;
     for (int j = lane; j < c.n; j += 64) {
         const int pi = (int)c.id[j], pt = (int)c.tr[j];
         const float xi = xr[pi], xt = xr[pt];
@@ -698,53 +784,40 @@ __device__ __forceinline__ void density_bwd_row(const CouplingArgs &c, const flo
         float *guw = g_u + row * c.n * P + j * K;
         float *guh = guw + c.n * K;
         float *gud = g_u + row * c.n * P + 2 * c.n * K + j * (K + 1);
-        float gw[K], gh[K], gd[K + 1];
+        float gw[B::cap], gh[B::cap], gd[B::cap + 1];
         if (part == 1) {
         } else if (xt >= -c.bound && xt <= c.bound) {
             const float *p = params + (row * c.n + j) * P;
-            float w[K], h[K];
-            cond_params<K>(p, c.sq, w, h);
+            float w[B::cap], h[B::cap];
+            cond_params(bins, p, c.sq, w, h);
             float g;
-            rqs_point_bwd<K, false>(xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, gd);
+            bins_point_bwd<false>(bins, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, adj_dst<B>(gd, gp + 2 * K));
             gx[row * c.D + pt] = g;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                gp[k] = gw[k] / c.sq;
-                gp[K + k] = gh[k] / c.sq;
-            }
-#pragma unroll
-            for (int k = 0; k <= K; ++k) gp[2 * K + k] = gd[k];
+            FS_BINS_FOR(k, K, gp[k] = gw[k] / c.sq; gp[K + k] = gh[k] / c.sq;)
+            if constexpr (B::fixed) FS_BINS_FOR(k, K + 1, gp[2 * K + k] = gd[k];)
         } else {
             gx[row * c.D + pt] = got;
-#pragma unroll
-            for (int k = 0; k < P; ++k) gp[k] = 0.f;
+            FS_BINS_FOR(k, P, gp[k] = 0.f;)
         }
         if (part == 0) {
         } else if (xi >= -c.bound && xi <= c.bound) {
             float g;
-            rqs_point_bwd<K, false>(xi, uw + j * K, uh + j * K, ud + j * (K + 1), c.bound, goi, gl, g, gw, gh, gd);
+            bins_point_bwd<false>(bins, xi, uw + j * K, uh + j * K, ud + j * (K + 1), c.bound, goi, gl, g,
+                                  adj_dst<B>(gw, guw), adj_dst<B>(gh, guh), adj_dst<B>(gd, gud));
             gx[row * c.D + pi] = g;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                guw[k] = gw[k];
-                guh[k] = gh[k];
+            if constexpr (B::fixed) {
+                FS_BINS_FOR(k, K, guw[k] = gw[k]; guh[k] = gh[k];)
+                FS_BINS_FOR(k, K + 1, gud[k] = gd[k];)
             }
-#pragma unroll
-            for (int k = 0; k <= K; ++k) gud[k] = gd[k];
         } else {
             gx[row * c.D + pi] = goi;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                guw[k] = 0.f;
-                guh[k] = 0.f;
-            }
-#pragma unroll
-            for (int k = 0; k <= K; ++k) gud[k] = 0.f;
+            FS_BINS_FOR(k, K, guw[k] = 0.f; guh[k] = 0.f;)
+            FS_BINS_FOR(k, K + 1, gud[k] = 0.f;)
         }
     }
 }
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_density_bwd_kernel(
     CouplingArgs c, const float *__restrict__ x, const float *__restrict__ params, const float *__restrict__ uw,
     const float *__restrict__ uh, const float *__restrict__ ud, const float *__restrict__ g_out,
@@ -752,8 +825,8 @@ __global__ __launch_bounds__(256) void coupling_density_bwd_kernel(
     const int wv = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * kCplRows + (wv >> 1);
     if (row >= c.rows) return;
-    density_bwd_row<K>(c, x, params, uw, uh, ud, g_out ? g_out + row * c.D : nullptr, g_lq, gx, g_params, g_u, row,
-                       wv & 1);
+    density_bwd_row(Bins<KT>{c.K}, c, x, params, uw, uh, ud, g_out ? g_out + row * c.D : nullptr, g_lq, gx, g_params,
+                    g_u, row, wv & 1);
 }
 
 // density direction, before the conditioner: t = [cos(s x_id), sin(s x_id)]
@@ -809,7 +882,7 @@ __global__ __launch_bounds__(256) void coupling_features_bwd_kernel(CouplingArgs
 // each exactly as fs_coupling_features_bwd then fs_coupling_density_bwd compute them.
 constexpr int kCplMaxDB = 256;
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_bwd_step_kernel(CouplingArgs cf, const float *__restrict__ xf,
                                                                 const float *__restrict__ g_t, float *gxf,
                                                                 const float *__restrict__ gx_add, CouplingArgs c,
@@ -828,7 +901,7 @@ __global__ __launch_bounds__(256) void coupling_bwd_step_kernel(CouplingArgs cf,
     if (live && (wv & 1) == 0) features_bwd_row(cf, xf, g_t, gxf, gx_add, row, rb);
     __syncthreads();
     if (!live) return;
-    density_bwd_row<K>(c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, wv & 1);
+    density_bwd_row(Bins<KT>{c.K}, c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, wv & 1);
 }
 
 // sampling direction (Coupling.inverse), forward only: roll, unconditional inverse spline
@@ -840,10 +913,10 @@ struct SamplePreArgs {
     int32_t *nan_flag;
 };
 
-template <int K>
-__device__ __forceinline__ void sample_pre_row(const CouplingArgs &c, const SamplePreArgs &s, int64_t row,
+template <class B>
+__device__ __forceinline__ void sample_pre_row(B bins, const CouplingArgs &c, const SamplePreArgs &s, int64_t row,
                                                const float *zr = nullptr) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, K = bins.k();
     if (!zr) zr = s.z + row * c.D;
     float su = 0.f;
     for (int j = lane; j < c.n; j += 64) {
@@ -851,7 +924,7 @@ __device__ __forceinline__ void sample_pre_row(const CouplingArgs &c, const Samp
         const float xi = zr[(pi + c.split) % c.D];
         float yi = xi, li = 0.f;
         if (xi >= -c.bound && xi <= c.bound)
-            rqs_point<K, true>(xi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, yi, li, s.nan_flag);
+            bins_point<true>(bins, xi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, yi, li, s.nan_flag);
         const float v = c.scale * yi;
         s.t[row * 2 * c.n + j] = cosf(v);
         s.t[row * 2 * c.n + c.n + j] = sinf(v);
@@ -863,10 +936,10 @@ __device__ __forceinline__ void sample_pre_row(const CouplingArgs &c, const Samp
     if (lane == 0) s.lad_u[row] = su;
 }
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_sample_pre_kernel(CouplingArgs c, SamplePreArgs s) {
     const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) sample_pre_row<K>(c, s, row);
+    if (row < c.rows) sample_pre_row(Bins<KT>{c.K}, c, s, row);
 }
 
 // ... then the conditional inverse spline of the transform half in place;
@@ -877,10 +950,10 @@ struct SamplePostArgs {
     int32_t *nan_flag;
 };
 
-template <int K>
-__device__ __forceinline__ void sample_post_row(const CouplingArgs &c, const SamplePostArgs &s, int64_t row,
+template <class B>
+__device__ __forceinline__ void sample_post_row(B bins, const CouplingArgs &c, const SamplePostArgs &s, int64_t row,
                                                 float *rb = nullptr) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, K = bins.k();
     float sc = 0.f;
     for (int j = lane; j < c.n; j += 64) {
         const int pt = (int)c.tr[j];
@@ -892,9 +965,9 @@ __device__ __forceinline__ void sample_post_row(const CouplingArgs &c, const Sam
         float yt = xt, lt = 0.f;
         if (xt >= -c.bound && xt <= c.bound) {
             const float *p = s.params + (row * c.n + j) * (3 * K + 1);
-            float w[K], h[K];
-            cond_params<K>(p, c.sq, w, h);
-            rqs_point<K, true>(xt, w, h, p + 2 * K, c.bound, yt, lt, s.nan_flag);
+            float w[B::cap], h[B::cap];
+            cond_params(bins, p, c.sq, w, h);
+            bins_point<true>(bins, xt, w, h, p + 2 * K, c.bound, yt, lt, s.nan_flag);
         }
         s.out[row * c.D + pt] = yt;
         if (rb) rb[pt] = yt;
@@ -904,36 +977,38 @@ __device__ __forceinline__ void sample_post_row(const CouplingArgs &c, const Sam
     if (lane == 0) s.lq_out[row] = (s.lq_in ? s.lq_in[row] : 0.f) - (s.lad_u[row] + sc);
 }
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_sample_post_kernel(CouplingArgs c, SamplePostArgs s) {
     const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) sample_post_row<K>(c, s, row);
+    if (row < c.rows) sample_post_row(Bins<KT>{c.K}, c, s, row);
 }
 
 // The training step's two passes side by side (fs_coupling_pair_pre / _post): workgroups
 // [0, nb0) run the sampling pass's layer (rows of cs), the rest the density pass's layer
 // (rows of cd), each row exactly as the single-pass kernels compute it.
-template <int K>
+// (both layers have the same bin count: cs.K)
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_pair_pre_kernel(CouplingArgs cs, SamplePreArgs s, CouplingArgs cd,
                                                                 const float *__restrict__ x, float *t, unsigned nb0) {
     const bool dens = blockIdx.x >= nb0;
     const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x) * kCplRows + (threadIdx.x >> 6);
     if (!dens) {
-        if (row < cs.rows) sample_pre_row<K>(cs, s, row);
+        if (row < cs.rows) sample_pre_row(Bins<KT>{cs.K}, cs, s, row);
     } else if (row < cd.rows) {
         features_row(cd, x, t, row);
     }
 }
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_pair_post_kernel(CouplingArgs cs, SamplePostArgs s, CouplingArgs cd,
                                                                  DensityFwdArgs d, unsigned nb0) {
+    const Bins<KT> bins{cs.K};
     const bool dens = blockIdx.x >= nb0;
     const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x) * kCplRows + (threadIdx.x >> 6);
     if (!dens) {
-        if (row < cs.rows) sample_post_row<K>(cs, s, row);
+        if (row < cs.rows) sample_post_row(bins, cs, s, row);
     } else if (row < cd.rows) {
-        density_fwd_row<K>(cd, d, row);
+        density_fwd_row(bins, cd, d, row);
     }
 }
 
@@ -945,10 +1020,11 @@ __global__ __launch_bounds__(256) void coupling_pair_post_kernel(CouplingArgs cs
 // it; one launch and one HBM round trip of the rows fewer per layer.
 constexpr int kCplMaxD = 256;
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_pair_step_kernel(CouplingArgs cs, SamplePostArgs s, CouplingArgs cs2,
                                                                  SamplePreArgs s2, CouplingArgs cd, DensityFwdArgs d,
                                                                  CouplingArgs cd2, float *t_d2, unsigned nb0) {
+    const Bins<KT> bins{cs.K};
     __shared__ float rbuf[kCplRows][kCplMaxD];
     float *rb = rbuf[threadIdx.x >> 6];
     const bool dens = blockIdx.x >= nb0;
@@ -956,14 +1032,14 @@ __global__ __launch_bounds__(256) void coupling_pair_step_kernel(CouplingArgs cs
     const bool live = dens ? row < cd.rows : row < cs.rows;
     if (live) {
         if (!dens)
-            sample_post_row<K>(cs, s, row, rb);
+            sample_post_row(bins, cs, s, row, rb);
         else
-            density_fwd_row<K>(cd, d, row, rb);
+            density_fwd_row(bins, cd, d, row, rb);
     }
     __syncthreads();  // the row's LDS copy, written by every lane of its wave
     if (!live) return;
     if (!dens)
-        sample_pre_row<K>(cs2, s2, row, rb);
+        sample_pre_row(bins, cs2, s2, row, rb);
     else
         features_row(cd2, d.out, t_d2, row, rb);
 }
@@ -978,40 +1054,39 @@ __global__ __launch_bounds__(256) void coupling_pair_step_kernel(CouplingArgs cs
 // results are bit-identical to coupling_pair_step_kernel / coupling_bwd_step_kernel
 // (tests/test_gpu_train.py).
 
-// knots c[0..K] of wave slot w (lane-major in kx: conflict-free)
-template <int K>
-__device__ __forceinline__ void knots_put(float *kx, int w, const float *c) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k <= K; ++k) kx[(w * (K + 1) + k) * 64 + lane] = c[k];
-}
-
-template <int K>
-__device__ __forceinline__ void knots_get(const float *kx, int w, float *c) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k <= K; ++k) c[k] = kx[(w * (K + 1) + k) * 64 + lane];
-}
-
-// this wave's knot set (own) and its partner's (slot w ^ 1) as (width, height) knots
-template <int K>
-__device__ __forceinline__ void knots_pair(float *kx, int w, int h, const float *own, float *wc, float *hc) {
-    knots_put<K>(kx, w, own);
+// this wave's knot set (own) into slot w of kx (K + 1 knots of 64 lanes each, lane-major:
+// conflict-free; the kernels reserve B::cap + 1 per slot) and, with its partner's (slot w ^ 1),
+// back as (width, height) knots
+template <class B>
+__device__ __forceinline__ void knots_pair(B bins, float *kx, int w, int h, const float *own, float *wc, float *hc) {
+    const int lane = threadIdx.x & 63, K = bins.k();
+#pragma unroll B::unroll
+    for (int k = 0; k <= K; ++k) kx[(w * (K + 1) + k) * 64 + lane] = own[k];
     __syncthreads();
-    float oc[K + 1];
-    knots_get<K>(kx, w ^ 1, oc);
+    if constexpr (B::fixed) {  // all the partner's knots first, then the selects
+        float oc[B::cap + 1];
 #pragma unroll
-    for (int k = 0; k <= K; ++k) {
-        wc[k] = h == 0 ? own[k] : oc[k];
-        hc[k] = h == 0 ? oc[k] : own[k];
+        for (int k = 0; k <= K; ++k) oc[k] = kx[((w ^ 1) * (K + 1) + k) * 64 + lane];
+#pragma unroll
+        for (int k = 0; k <= K; ++k) {
+            wc[k] = h == 0 ? own[k] : oc[k];
+            hc[k] = h == 0 ? oc[k] : own[k];
+        }
+    } else {
+#pragma unroll 4
+        for (int k = 0; k <= K; ++k) {
+            const float oc = kx[((w ^ 1) * (K + 1) + k) * 64 + lane];
+            wc[k] = h == 0 ? own[k] : oc;
+            hc[k] = h == 0 ? oc : own[k];
+        }
     }
 }
 
 // sample_post_row on a wave pair (h: this wave's knot set); the lower wave stores
-template <int K>
-__device__ __forceinline__ void sample_post_row2(const CouplingArgs &c, const SamplePostArgs &s, int64_t row, float *rb,
-                                                 float *kx, int h) {
-    const int lane = threadIdx.x & 63;
+template <class B>
+__device__ __forceinline__ void sample_post_row2(B bins, const CouplingArgs &c, const SamplePostArgs &s, int64_t row,
+                                                 float *rb, float *kx, int h) {
+    const int lane = threadIdx.x & 63, K = bins.k();
     float sc = 0.f;
     for (int j0 = 0; j0 < c.n; j0 += 64) {  // uniform trip count: the pair meets at its barriers
         const int j = j0 + lane;
@@ -1024,18 +1099,17 @@ __device__ __forceinline__ void sample_post_row2(const CouplingArgs &c, const Sa
         }
         const float xt = s.out[row * c.D + pt];
         const float *p = s.params + (row * c.n + jj) * (3 * K + 1);
-        Knots<K> kn;
+        typename B::KnotSet kn;
         {
-            float u[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) u[k] = p[h * K + k] / c.sq;  // cond_params' half
-            build_knots<K>(u, c.bound, kn);
+            float u[B::cap];
+            FS_BINS_FOR(k, K, u[k] = p[h * K + k] / c.sq;)  // cond_params' half
+            bins_build_knots(bins, u, c.bound, kn);
         }
-        float wc[K + 1], hc[K + 1];
-        knots_pair<K>(kx, h, h, kn.c, wc, hc);
+        float wc[B::cap + 1], hc[B::cap + 1];
+        knots_pair(bins, kx, h, h, kn.c, wc, hc);
         float yt = xt, lt = 0.f;
         if (on && xt >= -c.bound && xt <= c.bound)
-            rqs_eval_knots<K, true>(xt, wc, hc, p + 2 * K, yt, lt, h == 0 ? s.nan_flag : nullptr);
+            bins_eval_knots<true>(bins, xt, wc, hc, p + 2 * K, yt, lt, h == 0 ? s.nan_flag : nullptr);
         if (h == 0 && on) {
             s.out[row * c.D + pt] = yt;
             rb[pt] = yt;
@@ -1049,10 +1123,10 @@ __device__ __forceinline__ void sample_post_row2(const CouplingArgs &c, const Sa
 
 // sample_pre_row on a wave pair: the lower wave stores the cosines and the row, the upper
 // one the sines
-template <int K>
-__device__ __forceinline__ void sample_pre_row2(const CouplingArgs &c, const SamplePreArgs &s, int64_t row,
+template <class B>
+__device__ __forceinline__ void sample_pre_row2(B bins, const CouplingArgs &c, const SamplePreArgs &s, int64_t row,
                                                 const float *zr, float *kx, int h) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, K = bins.k();
     float su = 0.f;
     for (int j0 = 0; j0 < c.n; j0 += 64) {
         const int j = j0 + lane;
@@ -1060,13 +1134,13 @@ __device__ __forceinline__ void sample_pre_row2(const CouplingArgs &c, const Sam
         const int jj = on ? j : 0;
         const int pi = (int)c.id[jj], pt = (int)c.tr[jj];
         const float xi = zr[(pi + c.split) % c.D];
-        Knots<K> kn;
-        build_knots<K>((h == 0 ? s.uw : s.uh) + jj * K, c.bound, kn);
-        float wc[K + 1], hc[K + 1];
-        knots_pair<K>(kx, h, h, kn.c, wc, hc);
+        typename B::KnotSet kn;
+        bins_build_knots(bins, (h == 0 ? s.uw : s.uh) + jj * K, c.bound, kn);
+        float wc[B::cap + 1], hc[B::cap + 1];
+        knots_pair(bins, kx, h, h, kn.c, wc, hc);
         float yi = xi, li = 0.f;
         if (on && xi >= -c.bound && xi <= c.bound)
-            rqs_eval_knots<K, true>(xi, wc, hc, s.ud + jj * (K + 1), yi, li, h == 0 ? s.nan_flag : nullptr);
+            bins_eval_knots<true>(bins, xi, wc, hc, s.ud + jj * (K + 1), yi, li, h == 0 ? s.nan_flag : nullptr);
         const float v = c.scale * yi;
         if (on) {
             if (h == 0) {
@@ -1086,10 +1160,10 @@ __device__ __forceinline__ void sample_pre_row2(const CouplingArgs &c, const Sam
 
 // density_fwd_row on a wave pair: wave 0 the conditional spline of the transform half,
 // wave 1 the unconditional one of the identity half; the log-det sums meet in red
-template <int K>
-__device__ __forceinline__ float density_fwd_row2(const CouplingArgs &c, const DensityFwdArgs &d, int64_t row, float *rb,
-                                                  float *red, int h) {
-    const int lane = threadIdx.x & 63;
+template <class B>
+__device__ __forceinline__ float density_fwd_row2(B bins, const CouplingArgs &c, const DensityFwdArgs &d, int64_t row,
+                                                  float *rb, float *red, int h) {
+    const int lane = threadIdx.x & 63, K = bins.k();
     const float *xr = d.x + row * c.D;
     float sl = 0.f;
     for (int j = lane; j < c.n; j += 64) {
@@ -1099,9 +1173,9 @@ __device__ __forceinline__ float density_fwd_row2(const CouplingArgs &c, const D
             float yt = xt, lt = 0.f;
             if (xt >= -c.bound && xt <= c.bound) {
                 const float *p = d.params + (row * c.n + j) * (3 * K + 1);
-                float w[K], hh[K];
-                cond_params<K>(p, c.sq, w, hh);
-                rqs_point<K, false>(xt, w, hh, p + 2 * K, c.bound, yt, lt, nullptr);
+                float w[B::cap], hh[B::cap];
+                cond_params(bins, p, c.sq, w, hh);
+                bins_point<false>(bins, xt, w, hh, p + 2 * K, c.bound, yt, lt, nullptr);
             }
             d.out[row * c.D + (pt + c.D - c.split) % c.D] = yt;
             rb[(pt + c.D - c.split) % c.D] = yt;
@@ -1111,7 +1185,7 @@ __device__ __forceinline__ float density_fwd_row2(const CouplingArgs &c, const D
             const float xi = xr[pi];
             float yi = xi, li = 0.f;
             if (xi >= -c.bound && xi <= c.bound)
-                rqs_point<K, false>(xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
+                bins_point<false>(bins, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
             d.out[row * c.D + (pi + c.D - c.split) % c.D] = yi;
             rb[(pi + c.D - c.split) % c.D] = yi;
             sl += li;
@@ -1122,25 +1196,26 @@ __device__ __forceinline__ float density_fwd_row2(const CouplingArgs &c, const D
     return sl;
 }
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(128) void coupling_pair_step2_kernel(CouplingArgs cs, SamplePostArgs s, CouplingArgs cs2,
                                                                   SamplePreArgs s2, CouplingArgs cd, DensityFwdArgs d,
                                                                   CouplingArgs cd2, float *t_d2, unsigned nb0) {
+    const Bins<KT> bins{cs.K};
     __shared__ float rb[kCplMaxD];
-    __shared__ float kx[2 * (K + 1) * 64];
+    __shared__ float kx[2 * (Bins<KT>::cap + 1) * 64];
     __shared__ float red[1];
     const int h = (int)(threadIdx.x >> 6);
     const bool dens = blockIdx.x >= nb0;
     const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x);
     if (!dens) {
         if (row >= cs.rows) return;  // whole workgroup: no barrier is left waiting
-        sample_post_row2<K>(cs, s, row, rb, kx, h);
+        sample_post_row2(bins, cs, s, row, rb, kx, h);
         __syncthreads();  // the row in LDS
-        sample_pre_row2<K>(cs2, s2, row, rb, kx, h);
+        sample_pre_row2(bins, cs2, s2, row, rb, kx, h);
         return;
     }
     if (row >= cd.rows) return;
-    const float sl = density_fwd_row2<K>(cd, d, row, rb, red, h);
+    const float sl = density_fwd_row2(bins, cd, d, row, rb, red, h);
     __syncthreads();  // the row in LDS, the unconditional log-det sum in red
     const int lane = threadIdx.x & 63;
     if (h == 0 && lane == 0) d.lq_out[row] = (d.lq_in ? d.lq_in[row] : 0.f) + (sl + red[0]);  // density_fwd_row's order
@@ -1157,16 +1232,16 @@ __global__ __launch_bounds__(128) void coupling_pair_step2_kernel(CouplingArgs c
 // 1: the unconditional one's, as in density_bwd_row), h = wave & 1 the knot set it builds
 // and back-propagates (0 widths, 1 heights); the core adjoints are computed by both waves
 // of a part from the swapped knots
-template <int K>
-__device__ __forceinline__ void density_bwd_row4(const CouplingArgs &c, const float *__restrict__ x,
+template <class B>
+__device__ __forceinline__ void density_bwd_row4(B bins, const CouplingArgs &c, const float *__restrict__ x,
                                                  const float *__restrict__ params, const float *__restrict__ uw,
                                                  const float *__restrict__ uh, const float *__restrict__ ud,
                                                  const float *gor, const float *__restrict__ g_lq, float *gx,
                                                  float *g_params, float *g_u, int64_t row, float *kx) {
-    const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6), part = wv >> 1, h = wv & 1;
+    const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6), part = wv >> 1, h = wv & 1, K = bins.k();
     const float *xr = x + row * c.D;
     const float gl = g_lq ? g_lq[row] : 0.f;
-    constexpr int P = 3 * K + 1;
+    const int P = 3 * K + 1;
     for (int j0 = 0; j0 < c.n; j0 += 64) {
         const int j = j0 + lane;
         const bool on = j < c.n;
@@ -1176,65 +1251,90 @@ __device__ __forceinline__ void density_bwd_row4(const CouplingArgs &c, const fl
         const float xv = xr[pos];
         const float go = gor ? gor[(pos + c.D - c.split) % c.D] : 0.f;
         const float *p = params + (row * c.n + jj) * P;
-        Knots<K> kn;
+        typename B::KnotSet kn;
         if (part == 0) {
-            float u[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) u[k] = p[h * K + k] / c.sq;  // cond_params' half
-            build_knots<K>(u, c.bound, kn);
+            float u[B::cap];
+            FS_BINS_FOR(k, K, u[k] = p[h * K + k] / c.sq;)  // cond_params' half
+            bins_build_knots(bins, u, c.bound, kn);
         } else {
-            build_knots<K>((h == 0 ? uw : uh) + jj * K, c.bound, kn);
+            bins_build_knots(bins, (h == 0 ? uw : uh) + jj * K, c.bound, kn);
         }
-        float wc[K + 1], hc[K + 1];
-        knots_pair<K>(kx, wv, h, kn.c, wc, hc);
+        float wc[B::cap + 1], hc[B::cap + 1];
+        knots_pair(bins, kx, wv, h, kn.c, wc, hc);
         const bool inside = xv >= -c.bound && xv <= c.bound;
         float *gp = g_params + (row * c.n + jj) * P;
         // g_u row: [uw n*K | uh n*K | ud n*(K+1)], the parameters' own layouts back to back
         float *guw = g_u + row * c.n * P + jj * K;
         float *guh = guw + c.n * K;
         float *gud = g_u + row * c.n * P + 2 * c.n * K + jj * (K + 1);
-        if (on && inside) {
-            float g, gcw[K + 1], gch[K + 1], gd[K + 1];
-            rqs_bwd_core<K, false>(xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1), go, gl, g, gcw, gch, gd);
-            float gsel[K + 1], gk[K];
+        // each wave stores its knot set's parameter adjoints and, on h == 0, gx and the derivative
+        // logits' adjoints.  The two spline families hand back the knot adjoints differently
+        // (dense / sparse), and the stores keep the shape each had
+        if constexpr (B::fixed) {
+            if (on && inside) {
+                float g, gcw[B::cap + 1], gch[B::cap + 1], gd[B::cap + 1];
+                rqs_bwd_core<B::kt, false>(xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1), go, gl, g, gcw, gch,
+                                           gd);
+                float gsel[B::cap + 1], gk[B::cap];
 #pragma unroll
-            for (int k = 0; k <= K; ++k) gsel[k] = h == 0 ? gcw[k] : gch[k];
-            knots_backward<K>(kn, gsel, c.bound, gk);
-            if (part == 0) {
+                for (int k = 0; k <= K; ++k) gsel[k] = h == 0 ? gcw[k] : gch[k];
+                knots_backward<B::kt>(kn, gsel, c.bound, gk);
+                if (part == 0) {
 #pragma unroll
-                for (int k = 0; k < K; ++k) gp[h * K + k] = gk[k] / c.sq;
-                if (h == 0) {
-                    gx[row * c.D + pt] = g;
+                    for (int k = 0; k < K; ++k) gp[h * K + k] = gk[k] / c.sq;
+                    if (h == 0) {
+                        gx[row * c.D + pt] = g;
 #pragma unroll
-                    for (int k = 0; k <= K; ++k) gp[2 * K + k] = gd[k];
+                        for (int k = 0; k <= K; ++k) gp[2 * K + k] = gd[k];
+                    }
+                } else {
+                    float *gu = h == 0 ? guw : guh;
+#pragma unroll
+                    for (int k = 0; k < K; ++k) gu[k] = gk[k];
+                    if (h == 0) {
+                        gx[row * c.D + pi] = g;
+#pragma unroll
+                        for (int k = 0; k <= K; ++k) gud[k] = gd[k];
+                    }
                 }
-            } else {
-                float *gu = h == 0 ? guw : guh;
+            } else if (on) {
+                if (part == 0) {
 #pragma unroll
-                for (int k = 0; k < K; ++k) gu[k] = gk[k];
-                if (h == 0) {
-                    gx[row * c.D + pi] = g;
+                    for (int k = 0; k < K; ++k) gp[h * K + k] = 0.f;
+                    if (h == 0) {
+                        gx[row * c.D + pt] = go;
 #pragma unroll
-                    for (int k = 0; k <= K; ++k) gud[k] = gd[k];
+                        for (int k = 0; k <= K; ++k) gp[2 * K + k] = 0.f;
+                    }
+                } else {
+                    float *gu = h == 0 ? guw : guh;
+#pragma unroll
+                    for (int k = 0; k < K; ++k) gu[k] = 0.f;
+                    if (h == 0) {
+                        gx[row * c.D + pi] = go;
+#pragma unroll
+                        for (int k = 0; k <= K; ++k) gud[k] = 0.f;
+                    }
                 }
             }
-        } else if (on) {
-            if (part == 0) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) gp[h * K + k] = 0.f;
+        } else {
+            float *gk_out = part == 0 ? gp + h * K : (h == 0 ? guw : guh);
+            float *gd_out = part == 0 ? gp + 2 * K : gud;
+            if (on && inside) {
+                float g, gd[B::cap + 1], gk[B::cap];
+                const BinAdjoint a = rqs_bwd_core_any<false>(K, xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1),
+                                                             go, gl, g, gd);
+                knots_backward_any(K, kn, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
+                for (int k = 0; k < K; ++k) gk_out[k] = part == 0 ? gk[k] / c.sq : gk[k];
                 if (h == 0) {
-                    gx[row * c.D + pt] = go;
-#pragma unroll
-                    for (int k = 0; k <= K; ++k) gp[2 * K + k] = 0.f;
+                    gx[row * c.D + pos] = g;
+                    for (int k = 0; k <= K; ++k) gd_out[k] = gd[k];
                 }
-            } else {
-                float *gu = h == 0 ? guw : guh;
-#pragma unroll
-                for (int k = 0; k < K; ++k) gu[k] = 0.f;
+            } else if (on) {
+                for (int k = 0; k < K; ++k) gk_out[k] = 0.f;
                 if (h == 0) {
-                    gx[row * c.D + pi] = go;
-#pragma unroll
-                    for (int k = 0; k <= K; ++k) gud[k] = 0.f;
+                    gx[row * c.D + pos] = go;
+                    for (int k = 0; k <= K; ++k) gd_out[k] = 0.f;
                 }
             }
         }
@@ -1242,7 +1342,7 @@ __device__ __forceinline__ void density_bwd_row4(const CouplingArgs &c, const fl
     }
 }
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_bwd_step4_kernel(CouplingArgs cf, const float *__restrict__ xf,
                                                                  const float *__restrict__ g_t, float *gxf,
                                                                  const float *__restrict__ gx_add, CouplingArgs c,
@@ -1254,479 +1354,12 @@ __global__ __launch_bounds__(256) void coupling_bwd_step4_kernel(CouplingArgs cf
                                                                  const float *__restrict__ g_lq, float *gx,
                                                                  float *g_params, float *g_u) {
     __shared__ float rb[kCplMaxDB];
-    __shared__ float kx[4 * (K + 1) * 64];
+    __shared__ float kx[4 * (Bins<KT>::cap + 1) * 64];
     const int64_t row = blockIdx.x;
     if (row >= c.rows) return;  // whole workgroup
     if (threadIdx.x < 64) features_bwd_row(cf, xf, g_t, gxf, gx_add, row, rb);
     __syncthreads();
-    density_bwd_row4<K>(c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, kx);
-}
-
-// ---------------------------------------------------------------------------
-// Every coupling kernel above with K a run-time value, 1 <= K <= kAnyMaxK (fs_coupling.any_k:
-// the general-shape mode's training step at a bin count no kernel is instantiated for).
-// Separate copies rather than a K policy on the row functions above: the spline underneath
-// differs (rqs_point_any and its adjoint index per-thread arrays of kAnyMaxK in private
-// memory and keep the knot adjoints sparse, where the instantiated ones scan registers),
-// and the instantiated kernels stay the code they were.  Same layout (one wave per row,
-// lane = feature, the two- / four-wave variants of coupling_waves(), D <= kCplMaxD in the
-// step kernels), same operations in the same order, so each row is what the single-layer
-// entry points give, and at K in {5, 8, 15, 32} what the instantiated kernels give up to the
-// compiler's choice of instructions.
-__device__ __forceinline__ void cond_params_any(int K, const float *p, float sq, float *w, float *h) {
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-        w[k] = p[k] / sq;
-        h[k] = p[K + k] / sq;
-    }
-}
-
-__device__ __forceinline__ void density_fwd_row_any(int K, const CouplingArgs &c, const DensityFwdArgs &d, int64_t row,
-                                                    float *rb = nullptr) {
-    const int lane = threadIdx.x & 63;
-    const float *xr = d.x + row * c.D;
-    float sc = 0.f, su = 0.f;
-    for (int j = lane; j < c.n; j += 64) {
-        const int pi = (int)c.id[j], pt = (int)c.tr[j];
-        const float xi = xr[pi], xt = xr[pt];
-        float yt = xt, lt = 0.f;
-        if (xt >= -c.bound && xt <= c.bound) {
-            const float *p = d.params + (row * c.n + j) * (3 * K + 1);
-            float w[kAnyMaxK], h[kAnyMaxK];
-            cond_params_any(K, p, c.sq, w, h);
-            rqs_point_any<false>(K, xt, w, h, p + 2 * K, c.bound, yt, lt, nullptr);
-        }
-        float yi = xi, li = 0.f;
-        if (xi >= -c.bound && xi <= c.bound)
-            rqs_point_any<false>(K, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
-        d.out[row * c.D + (pt + c.D - c.split) % c.D] = yt;
-        d.out[row * c.D + (pi + c.D - c.split) % c.D] = yi;
-        if (rb) {
-            rb[(pt + c.D - c.split) % c.D] = yt;
-            rb[(pi + c.D - c.split) % c.D] = yi;
-        }
-        sc += lt;
-        su += li;
-    }
-    sc = wave_sum(sc);
-    su = wave_sum(su);
-    if (lane == 0) d.lq_out[row] = (d.lq_in ? d.lq_in[row] : 0.f) + (sc + su);
-}
-
-__global__ __launch_bounds__(256) void coupling_density_fwd_any_kernel(int K, CouplingArgs c, DensityFwdArgs d) {
-    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) density_fwd_row_any(K, c, d, row);
-}
-
-// density_bwd_row; the adjoints that need no rescaling go straight to their rows of g_params / g_u
-__device__ __forceinline__ void density_bwd_row_any(int K, const CouplingArgs &c, const float *__restrict__ x,
-                                                    const float *__restrict__ params, const float *__restrict__ uw,
-                                                    const float *__restrict__ uh, const float *__restrict__ ud,
-                                                    const float *gor, const float *__restrict__ g_lq, float *gx,
-                                                    float *g_params, float *g_u, int64_t row, int part) {
-    const int lane = threadIdx.x & 63;
-    const float *xr = x + row * c.D;
-    const float gl = g_lq ? g_lq[row] : 0.f;
-    const int P = 3 * K + 1;
-    for (int j = lane; j < c.n; j += 64) {
-        const int pi = (int)c.id[j], pt = (int)c.tr[j];
-        const float xi = xr[pi], xt = xr[pt];
-        const float got = gor ? gor[(pt + c.D - c.split) % c.D] : 0.f;
-        const float goi = gor ? gor[(pi + c.D - c.split) % c.D] : 0.f;
-        float *gp = g_params + (row * c.n + j) * P;
-        // g_u row: [uw n*K | uh n*K | ud n*(K+1)], the parameters' own layouts back to back
-        float *guw = g_u + row * c.n * P + j * K;
-        float *guh = guw + c.n * K;
-        float *gud = g_u + row * c.n * P + 2 * c.n * K + j * (K + 1);
-        if (part == 1) {
-        } else if (xt >= -c.bound && xt <= c.bound) {
-            const float *p = params + (row * c.n + j) * P;
-            float w[kAnyMaxK], h[kAnyMaxK], gw[kAnyMaxK], gh[kAnyMaxK];
-            cond_params_any(K, p, c.sq, w, h);
-            float g;
-            rqs_point_bwd_any<false>(K, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, gp + 2 * K);
-            gx[row * c.D + pt] = g;
-            for (int k = 0; k < K; ++k) {
-                gp[k] = gw[k] / c.sq;
-                gp[K + k] = gh[k] / c.sq;
-            }
-        } else {
-            gx[row * c.D + pt] = got;
-            for (int k = 0; k < P; ++k) gp[k] = 0.f;
-        }
-        if (part == 0) {
-        } else if (xi >= -c.bound && xi <= c.bound) {
-            float g;
-            rqs_point_bwd_any<false>(K, xi, uw + j * K, uh + j * K, ud + j * (K + 1), c.bound, goi, gl, g, guw, guh,
-                                     gud);
-            gx[row * c.D + pi] = g;
-        } else {
-            gx[row * c.D + pi] = goi;
-            for (int k = 0; k < K; ++k) {
-                guw[k] = 0.f;
-                guh[k] = 0.f;
-            }
-            for (int k = 0; k <= K; ++k) gud[k] = 0.f;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void coupling_density_bwd_any_kernel(
-    int K, CouplingArgs c, const float *__restrict__ x, const float *__restrict__ params,
-    const float *__restrict__ uw, const float *__restrict__ uh, const float *__restrict__ ud,
-    const float *__restrict__ g_out, const float *__restrict__ g_lq, float *gx, float *g_params, float *g_u) {
-    const int wv = threadIdx.x >> 6;
-    const int64_t row = (int64_t)blockIdx.x * kCplRows + (wv >> 1);
-    if (row >= c.rows) return;
-    density_bwd_row_any(K, c, x, params, uw, uh, ud, g_out ? g_out + row * c.D : nullptr, g_lq, gx, g_params, g_u,
-                        row, wv & 1);
-}
-
-__global__ __launch_bounds__(256) void coupling_bwd_step_any_kernel(
-    int K, CouplingArgs cf, const float *__restrict__ xf, const float *__restrict__ g_t, float *gxf,
-    const float *__restrict__ gx_add, CouplingArgs c, const float *__restrict__ x, const float *__restrict__ params,
-    const float *__restrict__ uw, const float *__restrict__ uh, const float *__restrict__ ud,
-    const float *__restrict__ g_lq, float *gx, float *g_params, float *g_u) {
-    __shared__ float rbuf[kCplRows][kCplMaxDB];
-    const int wv = threadIdx.x >> 6;
-    float *rb = rbuf[wv >> 1];
-    const int64_t row = (int64_t)blockIdx.x * kCplRows + (wv >> 1);
-    const bool live = row < c.rows;
-    if (live && (wv & 1) == 0) features_bwd_row(cf, xf, g_t, gxf, gx_add, row, rb);
-    __syncthreads();
-    if (!live) return;
-    density_bwd_row_any(K, c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, wv & 1);
-}
-
-__device__ __forceinline__ void sample_pre_row_any(int K, const CouplingArgs &c, const SamplePreArgs &s, int64_t row,
-                                                   const float *zr = nullptr) {
-    const int lane = threadIdx.x & 63;
-    if (!zr) zr = s.z + row * c.D;
-    float su = 0.f;
-    for (int j = lane; j < c.n; j += 64) {
-        const int pi = (int)c.id[j], pt = (int)c.tr[j];
-        const float xi = zr[(pi + c.split) % c.D];
-        float yi = xi, li = 0.f;
-        if (xi >= -c.bound && xi <= c.bound)
-            rqs_point_any<true>(K, xi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, yi, li, s.nan_flag);
-        const float v = c.scale * yi;
-        s.t[row * 2 * c.n + j] = cosf(v);
-        s.t[row * 2 * c.n + c.n + j] = sinf(v);
-        s.out[row * c.D + pi] = yi;
-        s.out[row * c.D + pt] = zr[(pt + c.split) % c.D];
-        su += li;
-    }
-    su = wave_sum(su);
-    if (lane == 0) s.lad_u[row] = su;
-}
-
-__global__ __launch_bounds__(256) void coupling_sample_pre_any_kernel(int K, CouplingArgs c, SamplePreArgs s) {
-    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) sample_pre_row_any(K, c, s, row);
-}
-
-__device__ __forceinline__ void sample_post_row_any(int K, const CouplingArgs &c, const SamplePostArgs &s, int64_t row,
-                                                    float *rb = nullptr) {
-    const int lane = threadIdx.x & 63;
-    float sc = 0.f;
-    for (int j = lane; j < c.n; j += 64) {
-        const int pt = (int)c.tr[j];
-        if (rb) {
-            const int pi = (int)c.id[j];
-            rb[pi] = s.out[row * c.D + pi];  // written by this layer's pre launch
-        }
-        const float xt = s.out[row * c.D + pt];
-        float yt = xt, lt = 0.f;
-        if (xt >= -c.bound && xt <= c.bound) {
-            const float *p = s.params + (row * c.n + j) * (3 * K + 1);
-            float w[kAnyMaxK], h[kAnyMaxK];
-            cond_params_any(K, p, c.sq, w, h);
-            rqs_point_any<true>(K, xt, w, h, p + 2 * K, c.bound, yt, lt, s.nan_flag);
-        }
-        s.out[row * c.D + pt] = yt;
-        if (rb) rb[pt] = yt;
-        sc += lt;
-    }
-    sc = wave_sum(sc);
-    if (lane == 0) s.lq_out[row] = (s.lq_in ? s.lq_in[row] : 0.f) - (s.lad_u[row] + sc);
-}
-
-__global__ __launch_bounds__(256) void coupling_sample_post_any_kernel(int K, CouplingArgs c, SamplePostArgs s) {
-    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) sample_post_row_any(K, c, s, row);
-}
-
-__global__ __launch_bounds__(256) void coupling_pair_pre_any_kernel(int K, CouplingArgs cs, SamplePreArgs s,
-                                                                    CouplingArgs cd, const float *__restrict__ x,
-                                                                    float *t, unsigned nb0) {
-    const bool dens = blockIdx.x >= nb0;
-    const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x) * kCplRows + (threadIdx.x >> 6);
-    if (!dens) {
-        if (row < cs.rows) sample_pre_row_any(K, cs, s, row);
-    } else if (row < cd.rows) {
-        features_row(cd, x, t, row);
-    }
-}
-
-__global__ __launch_bounds__(256) void coupling_pair_post_any_kernel(int K, CouplingArgs cs, SamplePostArgs s,
-                                                                     CouplingArgs cd, DensityFwdArgs d, unsigned nb0) {
-    const bool dens = blockIdx.x >= nb0;
-    const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x) * kCplRows + (threadIdx.x >> 6);
-    if (!dens) {
-        if (row < cs.rows) sample_post_row_any(K, cs, s, row);
-    } else if (row < cd.rows) {
-        density_fwd_row_any(K, cd, d, row);
-    }
-}
-
-__global__ __launch_bounds__(256) void coupling_pair_step_any_kernel(int K, CouplingArgs cs, SamplePostArgs s,
-                                                                     CouplingArgs cs2, SamplePreArgs s2,
-                                                                     CouplingArgs cd, DensityFwdArgs d,
-                                                                     CouplingArgs cd2, float *t_d2, unsigned nb0) {
-    __shared__ float rbuf[kCplRows][kCplMaxD];
-    float *rb = rbuf[threadIdx.x >> 6];
-    const bool dens = blockIdx.x >= nb0;
-    const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x) * kCplRows + (threadIdx.x >> 6);
-    const bool live = dens ? row < cd.rows : row < cs.rows;
-    if (live) {
-        if (!dens)
-            sample_post_row_any(K, cs, s, row, rb);
-        else
-            density_fwd_row_any(K, cd, d, row, rb);
-    }
-    __syncthreads();  // the row's LDS copy, written by every lane of its wave
-    if (!live) return;
-    if (!dens)
-        sample_pre_row_any(K, cs2, s2, row, rb);
-    else
-        features_row(cd2, d.out, t_d2, row, rb);
-}
-
-// knots_pair: this wave's knot set (own) into slot w of kx (kAnyMaxK + 1 knots of 64 lanes per
-// slot are reserved, K + 1 are used) and, with its partner's (slot w ^ 1), back as (width,
-// height) knots
-__device__ __forceinline__ void knots_pair_any(int K, float *kx, int w, int h, const float *own, float *wc,
-                                               float *hc) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll 4
-    for (int k = 0; k <= K; ++k) kx[(w * (K + 1) + k) * 64 + lane] = own[k];
-    __syncthreads();
-#pragma unroll 4
-    for (int k = 0; k <= K; ++k) {
-        const float oc = kx[((w ^ 1) * (K + 1) + k) * 64 + lane];
-        wc[k] = h == 0 ? own[k] : oc;
-        hc[k] = h == 0 ? oc : own[k];
-    }
-}
-
-__device__ __forceinline__ void sample_post_row2_any(int K, const CouplingArgs &c, const SamplePostArgs &s, int64_t row,
-                                                     float *rb, float *kx, int h) {
-    const int lane = threadIdx.x & 63;
-    float sc = 0.f;
-    for (int j0 = 0; j0 < c.n; j0 += 64) {  // uniform trip count: the pair meets at its barriers
-        const int j = j0 + lane;
-        const bool on = j < c.n;
-        const int jj = on ? j : 0;
-        const int pt = (int)c.tr[jj];
-        if (h == 0 && on) {
-            const int pi = (int)c.id[jj];
-            rb[pi] = s.out[row * c.D + pi];  // written by this layer's pre launch
-        }
-        const float xt = s.out[row * c.D + pt];
-        const float *p = s.params + (row * c.n + jj) * (3 * K + 1);
-        KnotsAny kn;
-        {
-            float u[kAnyMaxK];
-            for (int k = 0; k < K; ++k) u[k] = p[h * K + k] / c.sq;  // cond_params' half
-            build_knots_any(K, u, c.bound, kn);
-        }
-        float wc[kAnyMaxK + 1], hc[kAnyMaxK + 1];
-        knots_pair_any(K, kx, h, h, kn.c, wc, hc);
-        float yt = xt, lt = 0.f;
-        if (on && xt >= -c.bound && xt <= c.bound)
-            rqs_eval_knots_any<true>(K, xt, wc, hc, p + 2 * K, yt, lt, h == 0 ? s.nan_flag : nullptr);
-        if (h == 0 && on) {
-            s.out[row * c.D + pt] = yt;
-            rb[pt] = yt;
-        }
-        sc += on ? lt : 0.f;
-        __syncthreads();  // the partner has read this round's knots
-    }
-    sc = wave_sum(sc);
-    if (h == 0 && lane == 0) s.lq_out[row] = (s.lq_in ? s.lq_in[row] : 0.f) - (s.lad_u[row] + sc);
-}
-
-__device__ __forceinline__ void sample_pre_row2_any(int K, const CouplingArgs &c, const SamplePreArgs &s, int64_t row,
-                                                    const float *zr, float *kx, int h) {
-    const int lane = threadIdx.x & 63;
-    float su = 0.f;
-    for (int j0 = 0; j0 < c.n; j0 += 64) {
-        const int j = j0 + lane;
-        const bool on = j < c.n;
-        const int jj = on ? j : 0;
-        const int pi = (int)c.id[jj], pt = (int)c.tr[jj];
-        const float xi = zr[(pi + c.split) % c.D];
-        KnotsAny kn;
-        build_knots_any(K, (h == 0 ? s.uw : s.uh) + jj * K, c.bound, kn);
-        float wc[kAnyMaxK + 1], hc[kAnyMaxK + 1];
-        knots_pair_any(K, kx, h, h, kn.c, wc, hc);
-        float yi = xi, li = 0.f;
-        if (on && xi >= -c.bound && xi <= c.bound)
-            rqs_eval_knots_any<true>(K, xi, wc, hc, s.ud + jj * (K + 1), yi, li, h == 0 ? s.nan_flag : nullptr);
-        const float v = c.scale * yi;
-        if (on) {
-            if (h == 0) {
-                s.t[row * 2 * c.n + j] = cosf(v);
-                s.out[row * c.D + pi] = yi;
-                s.out[row * c.D + pt] = zr[(pt + c.split) % c.D];
-            } else {
-                s.t[row * 2 * c.n + c.n + j] = sinf(v);
-            }
-        }
-        su += on ? li : 0.f;
-        __syncthreads();
-    }
-    su = wave_sum(su);
-    if (h == 0 && lane == 0) s.lad_u[row] = su;
-}
-
-__device__ __forceinline__ float density_fwd_row2_any(int K, const CouplingArgs &c, const DensityFwdArgs &d,
-                                                      int64_t row, float *rb, float *red, int h) {
-    const int lane = threadIdx.x & 63;
-    const float *xr = d.x + row * c.D;
-    float sl = 0.f;
-    for (int j = lane; j < c.n; j += 64) {
-        if (h == 0) {
-            const int pt = (int)c.tr[j];
-            const float xt = xr[pt];
-            float yt = xt, lt = 0.f;
-            if (xt >= -c.bound && xt <= c.bound) {
-                const float *p = d.params + (row * c.n + j) * (3 * K + 1);
-                float w[kAnyMaxK], hh[kAnyMaxK];
-                cond_params_any(K, p, c.sq, w, hh);
-                rqs_point_any<false>(K, xt, w, hh, p + 2 * K, c.bound, yt, lt, nullptr);
-            }
-            d.out[row * c.D + (pt + c.D - c.split) % c.D] = yt;
-            rb[(pt + c.D - c.split) % c.D] = yt;
-            sl += lt;
-        } else {
-            const int pi = (int)c.id[j];
-            const float xi = xr[pi];
-            float yi = xi, li = 0.f;
-            if (xi >= -c.bound && xi <= c.bound)
-                rqs_point_any<false>(K, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
-            d.out[row * c.D + (pi + c.D - c.split) % c.D] = yi;
-            rb[(pi + c.D - c.split) % c.D] = yi;
-            sl += li;
-        }
-    }
-    sl = wave_sum(sl);
-    if (h == 1 && lane == 0) red[0] = sl;
-    return sl;
-}
-
-__global__ __launch_bounds__(128) void coupling_pair_step2_any_kernel(int K, CouplingArgs cs, SamplePostArgs s,
-                                                                      CouplingArgs cs2, SamplePreArgs s2,
-                                                                      CouplingArgs cd, DensityFwdArgs d,
-                                                                      CouplingArgs cd2, float *t_d2, unsigned nb0) {
-    __shared__ float rb[kCplMaxD];
-    __shared__ float kx[2 * (kAnyMaxK + 1) * 64];
-    __shared__ float red[1];
-    const int h = (int)(threadIdx.x >> 6);
-    const bool dens = blockIdx.x >= nb0;
-    const int64_t row = (int64_t)(dens ? blockIdx.x - nb0 : blockIdx.x);
-    if (!dens) {
-        if (row >= cs.rows) return;  // whole workgroup: no barrier is left waiting
-        sample_post_row2_any(K, cs, s, row, rb, kx, h);
-        __syncthreads();  // the row in LDS
-        sample_pre_row2_any(K, cs2, s2, row, rb, kx, h);
-        return;
-    }
-    if (row >= cd.rows) return;
-    const float sl = density_fwd_row2_any(K, cd, d, row, rb, red, h);
-    __syncthreads();  // the row in LDS, the unconditional log-det sum in red
-    const int lane = threadIdx.x & 63;
-    if (h == 0 && lane == 0) d.lq_out[row] = (d.lq_in ? d.lq_in[row] : 0.f) + (sl + red[0]);  // density_fwd_row's order
-    for (int j = lane; j < cd2.n; j += 64) {  // features_row, cosines on wave 0, sines on wave 1
-        const float v = cd2.scale * rb[cd2.id[j]];
-        if (h == 0)
-            t_d2[row * 2 * cd2.n + j] = cosf(v);
-        else
-            t_d2[row * 2 * cd2.n + cd2.n + j] = sinf(v);
-    }
-}
-
-__device__ __forceinline__ void density_bwd_row4_any(int K, const CouplingArgs &c, const float *__restrict__ x,
-                                                     const float *__restrict__ params, const float *__restrict__ uw,
-                                                     const float *__restrict__ uh, const float *__restrict__ ud,
-                                                     const float *gor, const float *__restrict__ g_lq, float *gx,
-                                                     float *g_params, float *g_u, int64_t row, float *kx) {
-    const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6), part = wv >> 1, h = wv & 1;
-    const float *xr = x + row * c.D;
-    const float gl = g_lq ? g_lq[row] : 0.f;
-    const int P = 3 * K + 1;
-    for (int j0 = 0; j0 < c.n; j0 += 64) {
-        const int j = j0 + lane;
-        const bool on = j < c.n;
-        const int jj = on ? j : 0;
-        const int pi = (int)c.id[jj], pt = (int)c.tr[jj];
-        const int pos = part == 0 ? pt : pi;
-        const float xv = xr[pos];
-        const float go = gor ? gor[(pos + c.D - c.split) % c.D] : 0.f;
-        const float *p = params + (row * c.n + jj) * P;
-        KnotsAny kn;
-        if (part == 0) {
-            float u[kAnyMaxK];
-            for (int k = 0; k < K; ++k) u[k] = p[h * K + k] / c.sq;  // cond_params' half
-            build_knots_any(K, u, c.bound, kn);
-        } else {
-            build_knots_any(K, (h == 0 ? uw : uh) + jj * K, c.bound, kn);
-        }
-        float wc[kAnyMaxK + 1], hc[kAnyMaxK + 1];
-        knots_pair_any(K, kx, wv, h, kn.c, wc, hc);
-        const bool inside = xv >= -c.bound && xv <= c.bound;
-        float *gp = g_params + (row * c.n + jj) * P;
-        // g_u row: [uw n*K | uh n*K | ud n*(K+1)], the parameters' own layouts back to back
-        float *guw = g_u + row * c.n * P + jj * K;
-        float *guh = guw + c.n * K;
-        float *gud = g_u + row * c.n * P + 2 * c.n * K + jj * (K + 1);
-        // what this wave stores: its knot set's parameter adjoints and, on h == 0, gx and the
-        // derivative logits' adjoints
-        float *gk_out = part == 0 ? gp + h * K : (h == 0 ? guw : guh);
-        float *gd_out = part == 0 ? gp + 2 * K : gud;
-        if (on && inside) {
-            float g, gd[kAnyMaxK + 1], gk[kAnyMaxK];
-            const BinAdjoint a = rqs_bwd_core_any<false>(K, xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1), go,
-                                                         gl, g, gd);
-            knots_backward_any(K, kn, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
-            for (int k = 0; k < K; ++k) gk_out[k] = part == 0 ? gk[k] / c.sq : gk[k];
-            if (h == 0) {
-                gx[row * c.D + pos] = g;
-                for (int k = 0; k <= K; ++k) gd_out[k] = gd[k];
-            }
-        } else if (on) {
-            for (int k = 0; k < K; ++k) gk_out[k] = 0.f;
-            if (h == 0) {
-                gx[row * c.D + pos] = go;
-                for (int k = 0; k <= K; ++k) gd_out[k] = 0.f;
-            }
-        }
-        __syncthreads();  // the partners have read this round's knots
-    }
-}
-
-__global__ __launch_bounds__(256) void coupling_bwd_step4_any_kernel(
-    int K, CouplingArgs cf, const float *__restrict__ xf, const float *__restrict__ g_t, float *gxf,
-    const float *__restrict__ gx_add, CouplingArgs c, const float *__restrict__ x, const float *__restrict__ params,
-    const float *__restrict__ uw, const float *__restrict__ uh, const float *__restrict__ ud,
-    const float *__restrict__ g_lq, float *gx, float *g_params, float *g_u) {
-    __shared__ float rb[kCplMaxDB];
-    __shared__ float kx[4 * (kAnyMaxK + 1) * 64];
-    const int64_t row = blockIdx.x;
-    if (row >= c.rows) return;  // whole workgroup
-    if (threadIdx.x < 64) features_bwd_row(cf, xf, g_t, gxf, gx_add, row, rb);
-    __syncthreads();
-    density_bwd_row4_any(K, c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, kx);
+    density_bwd_row4(Bins<KT>{c.K}, c, x, params, uw, uh, ud, rb, g_lq, gx, g_params, g_u, row, kx);
 }
 
 // ---------------------------------------------------------------------------
@@ -1753,13 +1386,13 @@ struct SampleBwdPreArgs {
     float *gz, *g_u;
 };
 
-template <int K>
-__device__ __forceinline__ void sample_bwd_post_row(const CouplingArgs &c, const SampleBwdPostArgs &s,
+template <class B>
+__device__ __forceinline__ void sample_bwd_post_row(B bins, const CouplingArgs &c, const SampleBwdPostArgs &s,
                                                     const float *gor, int64_t row) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, K = bins.k();
     const float *zr = s.z + row * c.D;
     const float gl = s.g_lq ? -s.g_lq[row] : 0.f;  // lq_out = lq_in - (... + lt)
-    constexpr int P = 3 * K + 1;
+    const int P = 3 * K + 1;
     for (int j = lane; j < c.n; j += 64) {
         const int pt = (int)c.tr[j];
         const int qt = (pt + c.split) % c.D;
@@ -1769,19 +1402,13 @@ __device__ __forceinline__ void sample_bwd_post_row(const CouplingArgs &c, const
         float g = got;
         if (xt >= -c.bound && xt <= c.bound) {
             const float *p = s.params + (row * c.n + j) * P;
-            float w[K], h[K], gw[K], gh[K], gd[K + 1];
-            cond_params<K>(p, c.sq, w, h);
-            rqs_point_bwd<K, true>(xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, gd);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                gp[k] = gw[k] / c.sq;
-                gp[K + k] = gh[k] / c.sq;
-            }
-#pragma unroll
-            for (int k = 0; k <= K; ++k) gp[2 * K + k] = gd[k];
+            float w[B::cap], h[B::cap], gw[B::cap], gh[B::cap], gd[B::cap + 1];
+            cond_params(bins, p, c.sq, w, h);
+            bins_point_bwd<true>(bins, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, adj_dst<B>(gd, gp + 2 * K));
+            FS_BINS_FOR(k, K, gp[k] = gw[k] / c.sq; gp[K + k] = gh[k] / c.sq;)
+            if constexpr (B::fixed) FS_BINS_FOR(k, K + 1, gp[2 * K + k] = gd[k];)
         } else {
-#pragma unroll
-            for (int k = 0; k < P; ++k) gp[k] = 0.f;
+            FS_BINS_FOR(k, P, gp[k] = 0.f;)
         }
         if (s.gz) s.gz[row * c.D + qt] = g;
     }
@@ -1789,13 +1416,13 @@ __device__ __forceinline__ void sample_bwd_post_row(const CouplingArgs &c, const
 
 // rb (the fused launch): the row's whole gz, this half as computed and the other half as
 // this layer's bwd_post launch wrote it (s.gz is not null then)
-template <int K>
-__device__ __forceinline__ void sample_bwd_pre_row(const CouplingArgs &c, const SampleBwdPreArgs &s,
+template <class B>
+__device__ __forceinline__ void sample_bwd_pre_row(B bins, const CouplingArgs &c, const SampleBwdPreArgs &s,
                                                    const float *gor, int64_t row, float *rb = nullptr) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, K = bins.k();
     const float *zr = s.z + row * c.D;
     const float gl = s.g_lq ? -s.g_lq[row] : 0.f;  // lq_out = lq_in - (li + ...)
-    constexpr int P = 3 * K + 1;
+    const int P = 3 * K + 1;
     for (int j = lane; j < c.n; j += 64) {
         const int pi = (int)c.id[j];
         const int qi = (pi + c.split) % c.D;
@@ -1809,24 +1436,16 @@ __device__ __forceinline__ void sample_bwd_pre_row(const CouplingArgs &c, const 
         float *gud = s.g_u + row * c.n * P + 2 * c.n * K + j * (K + 1);
         float g = gyi;
         if (zi >= -c.bound && zi <= c.bound) {
-            float gw[K], gh[K], gd[K + 1];
-            rqs_point_bwd<K, true>(zi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, gyi, gl, g, gw, gh,
-                                   gd);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                guw[k] = gw[k];
-                guh[k] = gh[k];
+            float gw[B::cap], gh[B::cap], gd[B::cap + 1];
+            bins_point_bwd<true>(bins, zi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, gyi, gl, g,
+                                 adj_dst<B>(gw, guw), adj_dst<B>(gh, guh), adj_dst<B>(gd, gud));
+            if constexpr (B::fixed) {
+                FS_BINS_FOR(k, K, guw[k] = gw[k]; guh[k] = gh[k];)
+                FS_BINS_FOR(k, K + 1, gud[k] = gd[k];)
             }
-#pragma unroll
-            for (int k = 0; k <= K; ++k) gud[k] = gd[k];
         } else {
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                guw[k] = 0.f;
-                guh[k] = 0.f;
-            }
-#pragma unroll
-            for (int k = 0; k <= K; ++k) gud[k] = 0.f;
+            FS_BINS_FOR(k, K, guw[k] = 0.f; guh[k] = 0.f;)
+            FS_BINS_FOR(k, K + 1, gud[k] = 0.f;)
         }
         if (s.gz) s.gz[row * c.D + qi] = g;
         if (rb) {
@@ -1837,127 +1456,38 @@ __device__ __forceinline__ void sample_bwd_pre_row(const CouplingArgs &c, const 
     }
 }
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_sample_bwd_post_kernel(CouplingArgs c, SampleBwdPostArgs s,
                                                                        const float *__restrict__ g_out) {
     const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) sample_bwd_post_row<K>(c, s, g_out ? g_out + row * c.D : nullptr, row);
+    if (row < c.rows) sample_bwd_post_row(Bins<KT>{c.K}, c, s, g_out ? g_out + row * c.D : nullptr, row);
 }
 
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_sample_bwd_pre_kernel(CouplingArgs c, SampleBwdPreArgs s,
                                                                       const float *__restrict__ g_out) {
     const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) sample_bwd_pre_row<K>(c, s, g_out ? g_out + row * c.D : nullptr, row);
+    if (row < c.rows) sample_bwd_pre_row(Bins<KT>{c.K}, c, s, g_out ? g_out + row * c.D : nullptr, row);
 }
 
 // The backward between two layers of the sampling pass in one launch
 // (fs_coupling_sample_bwd_step): layer l's bwd_pre, whose row of gz (kept in LDS, and written
 // out) is the output gradient of layer l - 1, then layer l - 1's bwd_post on that row, each
 // exactly as the two launches compute it.
-template <int K>
+template <int KT>
 __global__ __launch_bounds__(256) void coupling_sample_bwd_step_kernel(CouplingArgs c, SampleBwdPreArgs s,
                                                                        const float *__restrict__ g_out,
                                                                        CouplingArgs cp, SampleBwdPostArgs sp) {
+    const Bins<KT> bins{c.K};
     __shared__ float rbuf[kCplRows][kCplMaxDB];
     float *rb = rbuf[threadIdx.x >> 6];
     const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
     const bool live = row < c.rows;
-    if (live) sample_bwd_pre_row<K>(c, s, g_out ? g_out + row * c.D : nullptr, row, rb);
+    if (live) sample_bwd_pre_row(bins, c, s, g_out ? g_out + row * c.D : nullptr, row, rb);
     __syncthreads();
-    if (live) sample_bwd_post_row<K>(cp, sp, rb, row);
+    if (live) sample_bwd_post_row(bins, cp, sp, rb, row);
 }
-
-// ... and their runtime-K twins (see "Separate copies" above): rqs_point_bwd_any<true>, the
-// adjoints that need no rescaling written straight to their rows
-__device__ __forceinline__ void sample_bwd_post_row_any(int K, const CouplingArgs &c, const SampleBwdPostArgs &s,
-                                                        const float *gor, int64_t row) {
-    const int lane = threadIdx.x & 63;
-    const float *zr = s.z + row * c.D;
-    const float gl = s.g_lq ? -s.g_lq[row] : 0.f;
-    const int P = 3 * K + 1;
-    for (int j = lane; j < c.n; j += 64) {
-        const int pt = (int)c.tr[j];
-        const int qt = (pt + c.split) % c.D;
-        const float xt = zr[qt];
-        const float got = gor ? gor[pt] : 0.f;
-        float *gp = s.g_params + (row * c.n + j) * P;
-        float g = got;
-        if (xt >= -c.bound && xt <= c.bound) {
-            const float *p = s.params + (row * c.n + j) * P;
-            float w[kAnyMaxK], h[kAnyMaxK], gw[kAnyMaxK], gh[kAnyMaxK];
-            cond_params_any(K, p, c.sq, w, h);
-            rqs_point_bwd_any<true>(K, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, gp + 2 * K);
-            for (int k = 0; k < K; ++k) {
-                gp[k] = gw[k] / c.sq;
-                gp[K + k] = gh[k] / c.sq;
-            }
-        } else {
-            for (int k = 0; k < P; ++k) gp[k] = 0.f;
-        }
-        if (s.gz) s.gz[row * c.D + qt] = g;
-    }
-}
-
-__device__ __forceinline__ void sample_bwd_pre_row_any(int K, const CouplingArgs &c, const SampleBwdPreArgs &s,
-                                                       const float *gor, int64_t row, float *rb = nullptr) {
-    const int lane = threadIdx.x & 63;
-    const float *zr = s.z + row * c.D;
-    const float gl = s.g_lq ? -s.g_lq[row] : 0.f;
-    const int P = 3 * K + 1;
-    for (int j = lane; j < c.n; j += 64) {
-        const int pi = (int)c.id[j];
-        const int qi = (pi + c.split) % c.D;
-        const float zi = zr[qi];
-        const float v = c.scale * s.out[row * c.D + pi];
-        const float gc = s.g_t[row * 2 * c.n + j] * -sinf(v), gs = s.g_t[row * 2 * c.n + c.n + j] * cosf(v);
-        const float gyi = (gc * c.scale + gs * c.scale) + (gor ? gor[pi] : 0.f);
-        float *guw = s.g_u + row * c.n * P + j * K;
-        float *guh = guw + c.n * K;
-        float *gud = s.g_u + row * c.n * P + 2 * c.n * K + j * (K + 1);
-        float g = gyi;
-        if (zi >= -c.bound && zi <= c.bound) {
-            rqs_point_bwd_any<true>(K, zi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, gyi, gl, g, guw,
-                                    guh, gud);
-        } else {
-            for (int k = 0; k < K; ++k) {
-                guw[k] = 0.f;
-                guh[k] = 0.f;
-            }
-            for (int k = 0; k <= K; ++k) gud[k] = 0.f;
-        }
-        if (s.gz) s.gz[row * c.D + qi] = g;
-        if (rb) {
-            const int qt = ((int)c.tr[j] + c.split) % c.D;
-            rb[qi] = g;
-            rb[qt] = s.gz[row * c.D + qt];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void coupling_sample_bwd_post_any_kernel(int K, CouplingArgs c, SampleBwdPostArgs s,
-                                                                           const float *__restrict__ g_out) {
-    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) sample_bwd_post_row_any(K, c, s, g_out ? g_out + row * c.D : nullptr, row);
-}
-
-__global__ __launch_bounds__(256) void coupling_sample_bwd_pre_any_kernel(int K, CouplingArgs c, SampleBwdPreArgs s,
-                                                                          const float *__restrict__ g_out) {
-    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    if (row < c.rows) sample_bwd_pre_row_any(K, c, s, g_out ? g_out + row * c.D : nullptr, row);
-}
-
-__global__ __launch_bounds__(256) void coupling_sample_bwd_step_any_kernel(int K, CouplingArgs c, SampleBwdPreArgs s,
-                                                                           const float *__restrict__ g_out,
-                                                                           CouplingArgs cp, SampleBwdPostArgs sp) {
-    __shared__ float rbuf[kCplRows][kCplMaxDB];
-    float *rb = rbuf[threadIdx.x >> 6];
-    const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
-    const bool live = row < c.rows;
-    if (live) sample_bwd_pre_row_any(K, c, s, g_out ? g_out + row * c.D : nullptr, row, rb);
-    __syncthreads();
-    if (live) sample_bwd_post_row_any(K, cp, sp, rb, row);
-}
+#undef FS_BINS_FOR
 
 }  // namespace fs
 
@@ -2066,29 +1596,43 @@ static fs::CouplingArgs coupling_args(const fs_coupling *c) {
     a.bound = (float)c->tail_bound;
     a.scale = (float)(M_PI / c->tail_bound);  // scale * ident with the Python-float scale (nn.py:133)
     a.sq = (float)sqrt((double)c->hidden);     // np.sqrt(num_hidden_channels) (coupling.py:340)
+    a.K = c->K;
     return a;
 }
 
-// any_k descriptors: K in the runtime-K kernels' range (capi.cpp checks it with a message)
+// any_k descriptors: K in the Bins<0> kernels' range (capi.cpp checks it with a message)
 static bool any_k_ok(const fs_coupling *c) { return c->K >= 1 && c->K <= kAnyMaxK; }
 
-#define FS_COUPLING_LAUNCH(KERNEL, ...)                                                         \
-    const fs::CouplingArgs a = coupling_args(cp);                                               \
-    if (cp->any_k && !any_k_ok(cp)) return hipErrorInvalidValue;                                \
-    if (a.rows <= 0) return hipSuccess;                                                         \
-    const dim3 grid((unsigned)((a.rows + kCplRows - 1) / kCplRows)), block(64 * kCplRows);                                  \
-    if (cp->any_k) {                                                                            \
-        hipLaunchKernelGGL(KERNEL##_any_kernel, grid, block, 0, st, (int)cp->K, a, __VA_ARGS__); \
-        return hipGetLastError();                                                               \
-    }                                                                                           \
-    switch (cp->K) {                                                                            \
-    case 5: hipLaunchKernelGGL((KERNEL##_kernel<5>), grid, block, 0, st, a, __VA_ARGS__); break;   \
-    case 8: hipLaunchKernelGGL((KERNEL##_kernel<8>), grid, block, 0, st, a, __VA_ARGS__); break;   \
-    case 15: hipLaunchKernelGGL((KERNEL##_kernel<15>), grid, block, 0, st, a, __VA_ARGS__); break; \
-    case 32: hipLaunchKernelGGL((KERNEL##_kernel<32>), grid, block, 0, st, a, __VA_ARGS__); break; \
-    default: return hipErrorInvalidValue;                                                       \
-    }                                                                                           \
+// launch(Bins<KT>{}) with descriptor c's bin-count policy: Bins<0> with any_k, else the
+// instantiation for its K; hipErrorInvalidValue where there is none
+template <class F>
+static hipError_t with_bins(const fs_coupling *c, F launch) {
+    if (c->any_k) {
+        if (!any_k_ok(c)) return hipErrorInvalidValue;
+        launch(Bins<0>{});
+    } else {
+        switch (c->K) {
+        case 5: launch(Bins<5>{}); break;
+        case 8: launch(Bins<8>{}); break;
+        case 15: launch(Bins<15>{}); break;
+        case 32: launch(Bins<32>{}); break;
+        default: return hipErrorInvalidValue;
+        }
+    }
     return hipGetLastError();
+}
+#define FS_KT decltype(bins)::kt  // inside with_bins' launch(auto bins)
+
+// one wave per row (an any_k descriptor's K is refused before the 0-row return, an
+// uninstantiated K after it)
+#define FS_COUPLING_LAUNCH(KERNEL, ...)                                                                    \
+    const fs::CouplingArgs a = coupling_args(cp);                                                          \
+    if (cp->any_k && !any_k_ok(cp)) return hipErrorInvalidValue;                                           \
+    if (a.rows <= 0) return hipSuccess;                                                                    \
+    const dim3 grid((unsigned)((a.rows + kCplRows - 1) / kCplRows)), block(64 * kCplRows);                 \
+    return with_bins(cp, [&](auto bins) {                                                                  \
+        hipLaunchKernelGGL((KERNEL##_kernel<FS_KT>), grid, block, 0, st, a, __VA_ARGS__);                  \
+    });
 
 hipError_t fs_coupling_density_fwd_impl(const fs_coupling *cp, const float *x, const float *params, const float *uw,
                                         const float *uh, const float *ud, const float *lq_in, float *out, float *lq_out,
@@ -2104,21 +1648,10 @@ hipError_t fs_coupling_density_bwd_impl(const fs_coupling *cp, const float *x, c
     const fs::CouplingArgs a = coupling_args(cp);
     if (a.rows <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((a.rows + kCplRows - 1) / kCplRows);
-    if (cp->any_k) {
-        if (!any_k_ok(cp)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(coupling_density_bwd_any_kernel, dim3(grid), dim3(128 * kCplRows), 0, st, (int)cp->K, a, x,
-                           params, uw, uh, ud, g_out, g_lq, gx, g_params, g_u);
-        return hipGetLastError();
-    }
-#define FS_DB(KK)                                                                                                  \
-    if (cp->K == KK) {                                                                                             \
-        hipLaunchKernelGGL(coupling_density_bwd_kernel<KK>, dim3(grid), dim3(128 * kCplRows), 0, st, a, x, params, uw, \
-                           uh, ud, g_out, g_lq, gx, g_params, g_u);                                                \
-        return hipGetLastError();                                                                                  \
-    }
-    FS_DB(5) FS_DB(8) FS_DB(15) FS_DB(32)
-#undef FS_DB
-    return hipErrorInvalidValue;
+    return with_bins(cp, [&](auto bins) {
+        hipLaunchKernelGGL(coupling_density_bwd_kernel<FS_KT>, dim3(grid), dim3(128 * kCplRows), 0, st, a, x, params, uw,
+                           uh, ud, g_out, g_lq, gx, g_params, g_u);
+    });
 }
 
 hipError_t fs_coupling_bwd_step_impl(const fs_coupling *fp, const float *xf, const float *g_t, float *gxf,
@@ -2130,29 +1663,14 @@ hipError_t fs_coupling_bwd_step_impl(const fs_coupling *fp, const float *xf, con
     if (a.rows <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((a.rows + kCplRows - 1) / kCplRows);
     const bool four = coupling_waves() && a.rows <= 0x7fffffff;
-    if (cp->any_k) {
-        if (!any_k_ok(cp)) return hipErrorInvalidValue;
+    return with_bins(cp, [&](auto bins) {
         if (four)
-            hipLaunchKernelGGL(coupling_bwd_step4_any_kernel, dim3((unsigned)a.rows), dim3(256), 0, st, (int)cp->K, af,
-                               xf, g_t, gxf, gx_add, a, x, params, uw, uh, ud, g_lq, gx, g_params, g_u);
+            hipLaunchKernelGGL(coupling_bwd_step4_kernel<FS_KT>, dim3((unsigned)a.rows), dim3(256), 0, st, af, xf, g_t,
+                               gxf, gx_add, a, x, params, uw, uh, ud, g_lq, gx, g_params, g_u);
         else
-            hipLaunchKernelGGL(coupling_bwd_step_any_kernel, dim3(grid), dim3(128 * kCplRows), 0, st, (int)cp->K, af,
-                               xf, g_t, gxf, gx_add, a, x, params, uw, uh, ud, g_lq, gx, g_params, g_u);
-        return hipGetLastError();
-    }
-#define FS_DB(KK)                                                                                                  \
-    if (cp->K == KK) {                                                                                             \
-        if (four)                                                                                                  \
-            hipLaunchKernelGGL(coupling_bwd_step4_kernel<KK>, dim3((unsigned)a.rows), dim3(256), 0, st, af, xf, g_t, \
-                               gxf, gx_add, a, x, params, uw, uh, ud, g_lq, gx, g_params, g_u);                   \
-        else                                                                                                       \
-            hipLaunchKernelGGL(coupling_bwd_step_kernel<KK>, dim3(grid), dim3(128 * kCplRows), 0, st, af, xf, g_t,  \
-                               gxf, gx_add, a, x, params, uw, uh, ud, g_lq, gx, g_params, g_u);                   \
-        return hipGetLastError();                                                                                  \
-    }
-    FS_DB(5) FS_DB(8) FS_DB(15) FS_DB(32)
-#undef FS_DB
-    return hipErrorInvalidValue;
+            hipLaunchKernelGGL(coupling_bwd_step_kernel<FS_KT>, dim3(grid), dim3(128 * kCplRows), 0, st, af, xf, g_t,
+                               gxf, gx_add, a, x, params, uw, uh, ud, g_lq, gx, g_params, g_u);
+    });
 }
 
 hipError_t fs_coupling_sample_pre_impl(const fs_coupling *cp, const float *z, const float *uw, const float *uh,
@@ -2198,32 +1716,26 @@ hipError_t fs_coupling_sample_bwd_step_impl(const fs_coupling *cp, const float *
 }
 #undef FS_COUPLING_LAUNCH
 
-#define FS_PAIR_LAUNCH(KERNEL, ...)                                                                     \
-    const fs::CouplingArgs as = coupling_args(sp), ad = coupling_args(dp);                              \
+// the sampling layer's rows on workgroups [0, nb0), the density layer's after them; WAVES per
+// row, kCplRows rows per workgroup (one in the two-wave kernel)
+#define FS_PAIR_LAUNCH(KERNEL, WAVES, ...)                                                                     \
+    const fs::CouplingArgs as = coupling_args(sp), ad = coupling_args(dp);                                     \
     if (sp->K != dp->K || !sp->any_k != !dp->any_k || as.rows < 0 || ad.rows < 0) return hipErrorInvalidValue; \
-    if (sp->any_k && !any_k_ok(sp)) return hipErrorInvalidValue;                                        \
-    const unsigned nb0 = (unsigned)((as.rows + kCplRows - 1) / kCplRows);                              \
-    const unsigned nb = nb0 + (unsigned)((ad.rows + kCplRows - 1) / kCplRows);                         \
-    if (nb == 0) return hipSuccess;                                                                     \
-    const dim3 block(64 * kCplRows);                                                                    \
-    if (sp->any_k) {                                                                                    \
-        hipLaunchKernelGGL(KERNEL##_any_kernel, dim3(nb), block, 0, st, (int)sp->K, __VA_ARGS__, nb0);  \
-        return hipGetLastError();                                                                       \
-    }                                                                                                   \
-    switch (sp->K) {                                                                                    \
-    case 5: hipLaunchKernelGGL((KERNEL##_kernel<5>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;   \
-    case 8: hipLaunchKernelGGL((KERNEL##_kernel<8>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break;   \
-    case 15: hipLaunchKernelGGL((KERNEL##_kernel<15>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break; \
-    case 32: hipLaunchKernelGGL((KERNEL##_kernel<32>), dim3(nb), block, 0, st, __VA_ARGS__, nb0); break; \
-    default: return hipErrorInvalidValue;                                                               \
-    }                                                                                                   \
-    return hipGetLastError();
+    if (sp->any_k && !any_k_ok(sp)) return hipErrorInvalidValue;                                               \
+    constexpr int wg_rows = WAVES == 1 ? kCplRows : 1;                                                         \
+    const unsigned nb0 = (unsigned)((as.rows + wg_rows - 1) / wg_rows);                                        \
+    const unsigned nb = nb0 + (unsigned)((ad.rows + wg_rows - 1) / wg_rows);                                   \
+    if (nb == 0) return hipSuccess;                                                                            \
+    return with_bins(sp, [&](auto bins) {                                                                      \
+        hipLaunchKernelGGL((KERNEL##_kernel<FS_KT>), dim3(nb), dim3(64 * WAVES * wg_rows), 0, st, __VA_ARGS__, \
+                           nb0);                                                                               \
+    });
 
 hipError_t fs_coupling_pair_pre_impl(const fs_coupling *sp, const float *z, const float *uw, const float *uh,
                                      const float *ud, float *t, float *out, float *lad_u, int32_t *nan_flag,
                                      const fs_coupling *dp, const float *x, float *td, hipStream_t st) {
     const SamplePreArgs s{z, uw, uh, ud, t, out, lad_u, nan_flag};
-    FS_PAIR_LAUNCH(coupling_pair_pre, as, s, ad, x, td)
+    FS_PAIR_LAUNCH(coupling_pair_pre, 1, as, s, ad, x, td)
 }
 
 hipError_t fs_coupling_pair_post_impl(const fs_coupling *sp, const float *params, const float *lad_u,
@@ -2233,7 +1745,7 @@ hipError_t fs_coupling_pair_post_impl(const fs_coupling *sp, const float *params
                                       float *lq_out_d, hipStream_t st) {
     const SamplePostArgs s{params, lad_u, lq_in, out, lq_out, nan_flag};
     const DensityFwdArgs d{x, params_d, uw, uh, ud, lq_in_d, out_d, lq_out_d};
-    FS_PAIR_LAUNCH(coupling_pair_post, as, s, ad, d)
+    FS_PAIR_LAUNCH(coupling_pair_post, 1, as, s, ad, d)
 }
 
 hipError_t fs_coupling_pair_step_impl(const fs_coupling *sp, const float *params, const float *lad_u,
@@ -2251,28 +1763,12 @@ hipError_t fs_coupling_pair_step_impl(const fs_coupling *sp, const float *params
         sp2->D != sp->D || dp2->D != dp->D)
         return hipErrorInvalidValue;
     if (coupling_waves() && sp->rows + dp->rows <= 0x7fffffff) {  // one row per two-wave workgroup
-        const fs::CouplingArgs as = coupling_args(sp), ad = coupling_args(dp);
-        if (sp->K != dp->K || !sp->any_k != !dp->any_k || as.rows < 0 || ad.rows < 0) return hipErrorInvalidValue;
-        if (sp->any_k && !any_k_ok(sp)) return hipErrorInvalidValue;
-        const unsigned nb0 = (unsigned)as.rows, nb = nb0 + (unsigned)ad.rows;
-        if (nb == 0) return hipSuccess;
-        if (sp->any_k) {
-            hipLaunchKernelGGL(coupling_pair_step2_any_kernel, dim3(nb), dim3(128), 0, st, (int)sp->K, as, s, as2, s2,
-                               ad, d, ad2, t_d2, nb0);
-            return hipGetLastError();
-        }
-        switch (sp->K) {
-        case 5: hipLaunchKernelGGL(coupling_pair_step2_kernel<5>, dim3(nb), dim3(128), 0, st, as, s, as2, s2, ad, d, ad2, t_d2, nb0); break;
-        case 8: hipLaunchKernelGGL(coupling_pair_step2_kernel<8>, dim3(nb), dim3(128), 0, st, as, s, as2, s2, ad, d, ad2, t_d2, nb0); break;
-        case 15: hipLaunchKernelGGL(coupling_pair_step2_kernel<15>, dim3(nb), dim3(128), 0, st, as, s, as2, s2, ad, d, ad2, t_d2, nb0); break;
-        case 32: hipLaunchKernelGGL(coupling_pair_step2_kernel<32>, dim3(nb), dim3(128), 0, st, as, s, as2, s2, ad, d, ad2, t_d2, nb0); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+        FS_PAIR_LAUNCH(coupling_pair_step2, 2, as, s, as2, s2, ad, d, ad2, t_d2)
     }
-    FS_PAIR_LAUNCH(coupling_pair_step, as, s, as2, s2, ad, d, ad2, t_d2)
+    FS_PAIR_LAUNCH(coupling_pair_step, 1, as, s, as2, s2, ad, d, ad2, t_d2)
 }
 #undef FS_PAIR_LAUNCH
+#undef FS_KT
 
 hipError_t fs_coupling_features_fwd_impl(const fs_coupling *cp, const float *x, float *t, hipStream_t st) {
     const fs::CouplingArgs a = coupling_args(cp);
