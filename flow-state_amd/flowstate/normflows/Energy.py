@@ -36,9 +36,11 @@ class UniformParticle(nn.Module):
 
 class SimpleLJ(nn.Module):
     """Pairwise LJ energy of flow samples for reverse_kld (reference:
-    NF/normflows/Energy/SimpleLJ.py:5-41): minimum image in a box of 2*bound, an
-    extra particle at the origin, linear core below r = 0.82, no cutoff.  The
-    reference allocates its zero row on 'cuda' unconditionally; here it follows x."""
+    NF/normflows/Energy/SimpleLJ.py:5-41): each particle wrapped into the box of
+    2*bound (x - 2*bound*round(x / (2*bound))) but no minimum image between
+    particles (the differences of the wrapped positions are used as they are), an
+    extra particle at the origin, linear core below r = 0.82 (inclusive), no cutoff.
+    The reference allocates its zero row on 'cuda' unconditionally; here it follows x."""
 
     def __init__(self, dim, n_particles, temperature, bound):
         super().__init__()

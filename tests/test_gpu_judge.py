@@ -68,11 +68,19 @@ def test_reference_judge_traces_replay(N):
 
 
 def test_batched_bulk_judge_matches_oracle():
+    check_bulk_judge()
+
+
+def check_bulk_judge(beta=1.0):
+    """fs_metropolis_judge through the batched judges against OP.metropolis_judge at inverse
+    temperature beta (shared with test_gpu_physics_params.py).  Returns the bulk verdicts."""
     N, C, M = 16, 2048, 7
     L = float(np.sqrt(N / 0.03))
     rng = np.random.default_rng(3)
     init = np.mod(OP.fcc_lattice(N)[None] + rng.normal(0, 0.05, (C, N, 2)), L)
-    bmc = BatchedMonteCarlo(None, init, Physics(L, L), np.arange(42, 42 + C, dtype=np.uint64))
+    physics = Physics(L, L, temperature=1.0 / beta)
+    beta = physics.beta  # 1 / (1 / beta): the value the device holds
+    bmc = BatchedMonteCarlo(None, init, physics, np.arange(42, 42 + C, dtype=np.uint64))
     props = np.mod(init[:, None] + rng.normal(0, 0.2, (C, M, N, 2)), L).astype(np.float32)
     props[::5, 3, 1] = props[::5, 3, 0]  # overlaps: rejected without a draw
     E0 = bmc.E_old.cpu().numpy().copy()
@@ -81,7 +89,7 @@ def test_batched_bulk_judge_matches_oracle():
     acc, att = bmc.bulk_judge_normalizing_flow(torch.from_numpy(props), torch.from_numpy(ref))
     assert att == M
     E_new = OP.total_energy_batch(props.reshape(C * M, N, 2), OP.make_phys(N))[0].reshape(C, M)
-    acc_o = OP.metropolis_judge(ref, E_new, pcg0)
+    acc_o = OP.metropolis_judge(ref, E_new, pcg0, beta=beta)
     np.testing.assert_array_equal(acc.cpu().numpy(), acc_o.sum(1))
     np.testing.assert_array_equal(bmc.pcg.cpu().numpy().view(np.uint64), pcg0)
     # the running energy is left at each chain's last proposal (energy_calculator.py:121-203)
@@ -90,11 +98,12 @@ def test_batched_bulk_judge_matches_oracle():
     pcg1 = pcg0.copy()
     one = props[:, 0]
     a1 = bmc.judge_normalizing_flow(torch.from_numpy(one)).cpu().numpy()
-    np.testing.assert_array_equal(a1, OP.metropolis_judge(E_new[:, -1], E_new[:, :1], pcg1)[:, 0])
+    np.testing.assert_array_equal(a1, OP.metropolis_judge(E_new[:, -1], E_new[:, :1], pcg1, beta=beta)[:, 0])
     np.testing.assert_array_equal(bmc.pcg.cpu().numpy().view(np.uint64), pcg1)
     np.testing.assert_allclose(bmc.E_old.cpu().numpy(), E_new[:, -1], rtol=1e-12)
     assert (bmc.attempts.cpu().numpy() == 1).all()
     np.testing.assert_array_equal(bmc.state.cpu().numpy(), init)
+    return acc_o
 
 
 @pytest.mark.parametrize("tag", ["N16_f32", "N16_f64", "N64_f32", "N64_f64"])

@@ -161,18 +161,24 @@ def _random_batch(N, C, seed, spread):
                                      (33, 128, 200), (64, 256, 200)])
 def test_local_moves_match_oracle(N, C, moves):
     L, init, f32 = _random_batch(N, C, seed=N, spread=0.3)
+    check_local_moves(init, f32, moves, Physics(L, L), OP.make_phys(N), 1.0)
+
+
+def check_local_moves(init, f32, moves, physics, phys, beta):
+    """fs_local_moves on a mixed float32 / float64 batch against the oracle's LocalChain with
+    the same constants (shared with test_gpu_physics_params.py).  Returns the accept logs."""
+    C = len(init)
     state = np.where(f32[:, None, None], init.astype(np.float32).astype(np.float64), init)
     seeds = np.arange(1000, 1000 + C, dtype=np.uint64)
-    b = BatchedMonteCarlo(None, state, Physics(L, L), seeds, initial_max_displacement=0.65)
+    b = BatchedMonteCarlo(None, state, physics, seeds, initial_max_displacement=0.65)
     b.state_is_f32.copy_(torch.from_numpy(f32.astype(np.uint8)))
     b.E_old, b.W_old = b._energy_of_state()
     E0, W0 = b.E_old.cpu().numpy().copy(), b.W_old.cpu().numpy().copy()
     _, _, log = b.local_moves(moves, adjust_every=50, log_accepts=True)
     log = log.cpu().numpy()
-    phys = OP.make_phys(N)
     for c in range(C):
         pc = state[c].astype(np.float32) if f32[c] else state[c]
-        ch = OP.LocalChain(pc, int(seeds[c]), phys, E=E0[c], W=W0[c], max_disp=0.65)
+        ch = OP.LocalChain(pc, int(seeds[c]), phys, E=E0[c], W=W0[c], max_disp=0.65, beta=beta)
         ref = ch.local_moves(moves, adjust_every=50)
         np.testing.assert_array_equal(log[c], ref.astype(np.uint8), err_msg=f"chain {c}")
         np.testing.assert_array_equal(b.state[c].cpu().numpy(), ch.xy)
@@ -181,6 +187,7 @@ def test_local_moves_match_oracle(N, C, moves):
         np.testing.assert_array_equal(_u64(b.pcg[c]), ch.pcg[:4])
         np.testing.assert_array_equal(_u64(b.pcg_buf[c]), ch.pcg[4:])
         assert b.attempts[c].item() == ch.cnt[0] and b.accepted[c].item() == ch.cnt[1]
+    return log
 
 
 LAYOUTS = [(8, 1), (8, 2), (8, 4), (8, 8), (64, 1), (16, 4), (4, 16), (4, 8), (4, 4), (1, 4), (1, 8), (2, 4), (4, 1)]

@@ -116,6 +116,13 @@ def test_pcg64_seed_many_matches_oracle():
 
 @pytest.mark.parametrize("correct_sign", [False, True])
 def test_accept_mask_bit_exact(correct_sign):
+    check_accept_mask(correct_sign)
+
+
+def accept_inputs():
+    """(E_old, E_new, nll_old, lq_new, seeds) of the accept-mask checks: 5000 chains with
+    hard-core proposals, overlapping old states, proposals outside the base support and a
+    ratio of exactly 1."""
     C = 5000
     rng = np.random.default_rng(9)
     E_old = rng.normal(-50, 5, C)
@@ -128,8 +135,17 @@ def test_accept_mask_bit_exact(correct_sign):
     E_new[5] = E_old[5]
     lq_new[5] = -nll_old[5]  # ratio exactly 1: accept without a draw
     seeds = np.arange(42, 42 + C, dtype=np.uint64)
+    return E_old, E_new, nll_old, lq_new, seeds
+
+
+def check_accept_mask(correct_sign, beta=1.0):
+    """fs_mh_accept against OP.mh_accept at inverse temperature beta (shared with
+    test_gpu_physics_params.py).  Returns the verdicts."""
+    E_old, E_new, nll_old, lq_new, seeds = accept_inputs()
+    C = len(seeds)
     pcg_o = OP.pcg64_seed_many(seeds)
-    acc_o, _ = OP.mh_accept(E_old, E_new, nll_old, -lq_new.astype(np.float64), pcg_o, correct_sign=correct_sign)
+    acc_o, _ = OP.mh_accept(E_old, E_new, nll_old, -lq_new.astype(np.float64), pcg_o, beta=beta,
+                            correct_sign=correct_sign)
 
     d = lambda a, dt=torch.float64: torch.from_numpy(np.ascontiguousarray(a)).to(dt).cuda()
     Eo, Wo, No = d(E_old), d(np.zeros(C)), d(nll_old)
@@ -142,8 +158,8 @@ def test_accept_mask_bit_exact(correct_sign):
     accd = torch.zeros(C, dtype=torch.int64, device="cuda")
     nacc = torch.zeros(1, dtype=torch.int64, device="cuda")
     En, lq, Wn = d(E_new), d(lq_new, torch.float32), d(np.zeros(C))
-    _lib.check(L.fs_mh_accept(make_phys(10.0, 10.0), C, 16, _lib.ptr(Eo), _lib.ptr(Wo), _lib.ptr(No), _lib.ptr(En),
-                              _lib.ptr(Wn), _lib.ptr(lq), _lib.ptr(pcg), None, None, None, _lib.ptr(acc),
+    _lib.check(L.fs_mh_accept(make_phys(10.0, 10.0, beta=beta), C, 16, _lib.ptr(Eo), _lib.ptr(Wo), _lib.ptr(No),
+                              _lib.ptr(En), _lib.ptr(Wn), _lib.ptr(lq), _lib.ptr(pcg), None, None, None, _lib.ptr(acc),
                               _lib.ptr(att), _lib.ptr(accd), _lib.ptr(nacc), int(correct_sign), _lib.stream_ptr()),
                "fs_mh_accept")
     got = acc.cpu().numpy()
@@ -154,6 +170,7 @@ def test_accept_mask_bit_exact(correct_sign):
     newE = np.where(acc_o == 1, E_new, E_old)
     np.testing.assert_array_equal(Eo.cpu().numpy(), newE)
     assert 0.05 < acc_o.mean() < 0.95
+    return acc_o
 
 
 def test_hist2d_and_well_stats():
@@ -206,6 +223,10 @@ def test_hist2d_clustered_large(nedges):
 @pytest.mark.gpu
 @pytest.mark.parametrize("half_box_scale", [1.0, 0.8])
 def test_well_stats_matches_classify_particles(half_box_scale):
+    check_well_stats(half_box_scale, 1.2)
+
+
+def check_well_stats(half_box_scale, r0, spread=0.6):
     """fs_well_stats = calculate_well_statistics' all-in-A / all-in-B (utils.py:61-141)
     with box = 2*half_box on both axes and each chain in its own dtype: checked against
     the oracle's classify (pinned to the reference in test_oracle_analysis.py), also for
@@ -219,18 +240,18 @@ def test_well_stats_matches_classify_particles(half_box_scale):
     # most chains packed near one well, a spread around the radius
     centre = np.where(rng.random(C)[:, None] < 0.5, box / 4, 3 * box / 4)
     pos = np.empty((C, N, 2))
-    pos[..., 0] = centre + rng.normal(0, 0.6, (C, N))
-    pos[..., 1] = box / 2 + rng.normal(0, 0.6, (C, N))
+    pos[..., 0] = centre + rng.normal(0, spread, (C, N))
+    pos[..., 1] = box / 2 + rng.normal(0, spread, (C, N))
     is_f32 = (rng.random(C) < 0.5).astype(np.uint8)
     pos[is_f32 == 1] = pos[is_f32 == 1].astype(np.float32)
     counts = torch.zeros((C, 3), dtype=torch.int64, device="cuda")
     tpos, tf32 = torch.from_numpy(pos).cuda(), torch.from_numpy(is_f32).cuda()  # alive across the launch
-    _lib.check(_lib.load().fs_well_stats(_lib.ptr(tpos), _lib.ptr(tf32), C, N, hb, 1.2,
+    _lib.check(_lib.load().fs_well_stats(_lib.ptr(tpos), _lib.ptr(tf32), C, N, hb, r0,
                                          _lib.ptr(counts), _lib.stream_ptr()))
     got = counts.cpu().numpy()
     want = np.zeros((C, 3), np.int64)
     for dt, sel in ((np.float32, is_f32 == 1), (np.float64, is_f32 == 0)):
-        _, st, _ = OA.classify(pos[sel].astype(dt), hb, 1.2)
+        _, st, _ = OA.classify(pos[sel].astype(dt), hb, r0)
         want[sel, 0] = st == 1
         want[sel, 1] = st == 2
     want[:, 2] = 1
