@@ -347,6 +347,242 @@ __global__ void __launch_bounds__(256) sample_analysis_kernel(const float *__res
         if (h2[i]) atomicAdd(&hist[i], (unsigned long long)h2[i]);
 }
 
+// ---------------------------------------------------------------- importance weights
+// Log-weights lw = -beta E - (double)log_q of flow samples against the Boltzmann target and
+// their running statistics (include/flowstate.h 'Importance weights').  Two stream-ordered
+// launches per batch: iw_partial_kernel (one slot of partial sums per workgroup, shifted by
+// the workgroup's own maximum) and the one-wave iw_finish_kernel, which folds the slots in
+// workgroup order into the running block.  The launch boundary is the hand-off; no float
+// atomics, so the same inputs in the same batches give the same bits on any device.
+constexpr int kIwSlots = 1024;  // workgroups of the partial launch (grid-stride beyond 256 * 1024 rows)
+
+struct IwHeader {  // the first 64 bytes of the state block (flowstate.h)
+    double max_lw, s1, s2, sum_lw;
+    long long n, n_zero, n_bad, reserved;
+};
+struct IwSlot {
+    double max_lw, s1, s2, sum_lw;
+    long long n_zero, n_bad, pad0, pad1;
+};
+static_assert(sizeof(IwHeader) == 64 && sizeof(IwSlot) == 64, "state block layout");
+
+__device__ inline double wave_max(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// lane 0 ends with ((..) + (..)): a fixed tree over the 64 lanes
+__device__ inline double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+__device__ inline long long wave_sum_i(long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+// thread 0 returns the sum over the 256 threads: wave trees, then the four waves in order
+__device__ inline double block_sum(double v, double *red) {
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    v = wave_sum(v);
+    __syncthreads();  // red may still be read from the previous call
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// exp(a - b) for a <= b, 0 when a is -inf (b = -inf included: no inf - inf)
+__device__ inline double exp_shift(double a, double b) { return a == -INFINITY ? 0.0 : exp(a - b); }
+
+__global__ void iw_reset_kernel(IwHeader *h) {
+    if (threadIdx.x == 0) *h = IwHeader{-INFINITY, 0.0, 0.0, 0.0, 0, 0, 0, 0};
+}
+
+__global__ void __launch_bounds__(256) iw_partial_kernel(double beta, int64_t M, const double *__restrict__ E,
+                                                         const float *__restrict__ log_q, double *log_w,
+                                                         IwSlot *__restrict__ slots) {
+    __shared__ double red[4];
+    __shared__ long long redi[2][4];
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    const double nbeta = -beta;
+    double tmax = -INFINITY, tsum = 0.0;
+    long long nz = 0, nb = 0;
+    for (int64_t m = first; m < M; m += step) {
+        const double e = E[m];
+        const float q = log_q[m];
+        double lw;
+        if (!(q == q) || q == INFINITY || q == -INFINITY || !(e == e) || e == -INFINITY) {
+            lw = -INFINITY;  // bad row: never reaches a sum
+            ++nb;
+        } else {
+            const double t = nbeta * e;
+            lw = t - (double)q;
+            if (lw == -INFINITY) ++nz;  // hard-core overlap: weight 0
+            else tsum += lw;
+        }
+        log_w[m] = lw;
+        tmax = fmax(tmax, lw);
+    }
+    double wmax = wave_max(tmax);
+    if (lane == 0) red[wid] = wmax;
+    __syncthreads();
+    wmax = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    double s1 = 0.0, s2 = 0.0;
+    for (int64_t m = first; m < M; m += step) {
+        const double w = exp_shift(log_w[m], wmax);  // this thread's own store above
+        s1 += w;
+        s2 += w * w;
+    }
+    s1 = block_sum(s1, red);
+    s2 = block_sum(s2, red);
+    tsum = block_sum(tsum, red);
+    nz = wave_sum_i(nz);
+    nb = wave_sum_i(nb);
+    if (lane == 0) {
+        redi[0][wid] = nz;
+        redi[1][wid] = nb;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        slots[blockIdx.x] = IwSlot{wmax, s1, s2, tsum, redi[0][0] + redi[0][1] + redi[0][2] + redi[0][3],
+                                   redi[1][0] + redi[1][1] + redi[1][2] + redi[1][3], 0, 0};
+}
+
+// one wave: the batch's maximum, every slot and the old sums rescaled to it once, then the
+// slots added in workgroup order by lane 0
+__global__ void __launch_bounds__(64) iw_finish_kernel(IwHeader *h, const IwSlot *__restrict__ slots, int P,
+                                                       int64_t M) {
+    __shared__ double a1[kIwSlots], a2[kIwSlots];
+    const int lane = threadIdx.x;
+    const double old_max = h->max_lw;
+    double mx = old_max;
+    for (int p = lane; p < P; p += 64) mx = fmax(mx, slots[p].max_lw);
+    mx = wave_max(mx);
+    for (int p = lane; p < P; p += 64) {
+        const double f = exp_shift(slots[p].max_lw, mx);
+        a1[p] = slots[p].s1 * f;
+        a2[p] = slots[p].s2 * (f * f);
+    }
+    __syncthreads();
+    if (lane != 0) return;
+    const double f = exp_shift(old_max, mx);  // 1 exactly while the maximum stands
+    double s1 = h->s1 * f, s2 = h->s2 * (f * f), sl = h->sum_lw;
+    long long nz = h->n_zero, nb = h->n_bad;
+    for (int p = 0; p < P; ++p) {
+        s1 += a1[p];
+        s2 += a2[p];
+        sl += slots[p].sum_lw;
+        nz += slots[p].n_zero;
+        nb += slots[p].n_bad;
+    }
+    *h = IwHeader{mx, s1, s2, sl, h->n + (long long)M, nz, nb, 0};
+}
+
+// normalised weight exp(lw - max_lw) / S1 of a row; 0 for lw = -inf (or NaN) rows and while S1 = 0
+__device__ inline double iw_weight(double lw, double mx, double s1) {
+    if (!(lw > -INFINITY) || !(s1 > 0.0)) return 0.0;
+    return exp(lw - mx) / s1;
+}
+
+// Weighted g(r) and well populations: workgroup k < nr sums w~_m counts[m][k] / denom[k],
+// workgroup nr the three scalars.  Thread t adds its rows t, t + 256, .. in order, then
+// block_sum's fixed tree: bit-reproducible.
+__global__ void __launch_bounds__(256) weighted_reduce_kernel(const int32_t *__restrict__ counts, int64_t M, int nr,
+                                                              const double *__restrict__ denom,
+                                                              const uint8_t *__restrict__ wstate,
+                                                              const double *__restrict__ avg_x,
+                                                              const double *__restrict__ log_w,
+                                                              const IwHeader *__restrict__ h,
+                                                              double *__restrict__ g_w, double *__restrict__ scalars) {
+    __shared__ double red[4];
+    const double mx = h->max_lw, s1 = h->s1;
+    const int k = blockIdx.x;
+    if (k < nr) {
+        const double dk = denom[k];
+        double s = 0.0;
+        for (int64_t m = threadIdx.x; m < M; m += 256) {
+            const double w = iw_weight(log_w[m], mx, s1);
+            if (w > 0.0) s += w * ((double)counts[m * nr + k] / dk);
+        }
+        s = block_sum(s, red);
+        if (threadIdx.x == 0) g_w[k] = s;
+        return;
+    }
+    double pa = 0.0, pb = 0.0, ax = 0.0;
+    for (int64_t m = threadIdx.x; m < M; m += 256) {
+        const double w = iw_weight(log_w[m], mx, s1);
+        if (!(w > 0.0)) continue;
+        const int st = wstate[m];
+        if (st == 1) pa += w;
+        if (st == 2) pb += w;
+        ax += w * avg_x[m];
+    }
+    pa = block_sum(pa, red);
+    pb = block_sum(pb, red);
+    ax = block_sum(ax, red);
+    if (threadIdx.x == 0) {
+        scalars[0] = pa;
+        scalars[1] = pb;
+        scalars[2] = (pa > 0.0 && pb > 0.0) ? log(pb / pa) : 0.0;  // utils.py:92-96
+        scalars[3] = ax;
+    }
+}
+
+// Weighted 2-D histogram of the configurations (the rows of samples.npy): sample_analysis_kernel's
+// arrangement and binning rule on (double)(cfg - fl32(half_box)), the workgroup's bins float64
+// in LDS (nb * nb * 8 bytes), non-zero bins flushed by float64 atomic adds.
+__host__ __device__ inline int wh_lds_bytes(int nb) { return (((nb + 1) * 8 + 15) & ~15) + nb * nb * 8; }
+
+__global__ void __launch_bounds__(256) weighted_hist2d_kernel(const float *__restrict__ cfg, int64_t M, int N,
+                                                              double half_box, const double *__restrict__ edges2,
+                                                              int nb, const double *__restrict__ log_w,
+                                                              const IwHeader *__restrict__ h,
+                                                              double *__restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double *e2 = (double *)smem;
+    double *h2 = (double *)(smem + (((nb + 1) * 8 + 15) & ~15));
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int i = threadIdx.x; i < nb * nb; i += blockDim.x) h2[i] = 0.0;
+    for (int i = threadIdx.x; i <= nb; i += blockDim.x) e2[i] = edges2[i];
+    __syncthreads();
+    const double inv2 = (double)nb / (e2[nb] - e2[0]);
+    auto bin_of = [&](double v) {  // sample_analysis_kernel's
+        if (!(v >= e2[0])) return -1;
+        if (v >= e2[nb]) return v == e2[nb] ? nb - 1 : nb;
+        return bin_near(e2, nb, inv2, v);
+    };
+    const float hb = (float)half_box;
+    const double mx = h->max_lw, s1 = h->s1;
+    for (int64_t m0 = (int64_t)blockIdx.x * 4; m0 < M; m0 += (int64_t)gridDim.x * 4) {
+        const int64_t m = m0 + wid;
+        if (m >= M) continue;  // wave-uniform
+        const double w = iw_weight(log_w[m], mx, s1);
+        if (!(w > 0.0)) continue;  // wave-uniform
+        const float *q = cfg + m * (int64_t)N * 2;
+        int bin = -1;  // N <= 64: one particle per lane
+        if (lane < N) {
+            const float cx = q[2 * lane] - hb, cy = q[2 * lane + 1] - hb;
+            const int bx = bin_of((double)cx), by = bin_of((double)cy);
+            if (bx >= 0 && bx < nb && by >= 0 && by < nb) bin = bx * nb + by;
+        }
+        // the configuration's particles of one bin are counted first and added once, as
+        // w~ * count by the first of their lanes: one rounded add per configuration and bin
+        int cnt = 0;
+        bool first = true;
+        for (int l = 0; l < N; ++l) {
+            const int other = __builtin_amdgcn_readlane(bin, l);  // l is wave-uniform: v_readlane_b32
+            if (other == bin) {
+                ++cnt;
+                first = first && l >= lane;
+            }
+        }
+        if (bin >= 0 && first) atomicAdd(&h2[bin], w * (double)cnt);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nb * nb; i += blockDim.x)
+        if (h2[i] != 0.0) atomicAdd(&hist[i], h2[i]);
+}
+
 }  // namespace fs
 
 using namespace fs;
@@ -403,5 +639,49 @@ hipError_t fs_pair_hist_impl(const void *pos, int f32, int64_t M, int N, double 
 hipError_t fs_rdf_mean_impl(const int32_t *counts, int64_t M, int nb, const double *denom, double *g, hipStream_t st) {
     if (nb <= 0) return hipSuccess;
     hipLaunchKernelGGL(rdf_mean_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st, counts, M, nb, denom, g);
+    return hipGetLastError();
+}
+
+int64_t fs_iw_state_bytes_impl() { return (int64_t)sizeof(IwHeader) + (int64_t)kIwSlots * (int64_t)sizeof(IwSlot); }
+
+hipError_t fs_iw_reset_impl(void *state, hipStream_t st) {
+    hipLaunchKernelGGL(iw_reset_kernel, dim3(1), dim3(64), 0, st, (IwHeader *)state);
+    return hipGetLastError();
+}
+
+hipError_t fs_importance_weights_impl(double beta, int64_t M, const double *E, const float *log_q, double *log_w,
+                                      void *state, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    IwHeader *h = (IwHeader *)state;
+    IwSlot *slots = (IwSlot *)(h + 1);
+    // the grid is a function of M alone (never of the CU count): the same bits on any device
+    const int64_t want = (M + 255) / 256;
+    const int P = (int)(want < kIwSlots ? want : kIwSlots);
+    hipLaunchKernelGGL(iw_partial_kernel, dim3((unsigned)P), dim3(256), 0, st, beta, M, E, log_q, log_w, slots);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(iw_finish_kernel, dim3(1), dim3(64), 0, st, h, (const IwSlot *)slots, P, M);
+    return hipGetLastError();
+}
+
+hipError_t fs_weighted_reduce_impl(const int32_t *counts, int64_t M, int nr, const double *denom,
+                                   const uint8_t *wstate, const double *avg_x, const double *log_w, const void *state,
+                                   double *g_w, double *scalars, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    hipLaunchKernelGGL(weighted_reduce_kernel, dim3((unsigned)(nr + 1)), dim3(256), 0, st, counts, M, nr, denom, wstate,
+                       avg_x, log_w, (const IwHeader *)state, g_w, scalars);
+    return hipGetLastError();
+}
+
+hipError_t fs_weighted_hist2d_impl(const float *cfg, int64_t M, int N, double half_box, const double *edges2, int nb,
+                                   const double *log_w, const void *state, double *hist, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    static std::atomic<unsigned long long> lds_done{0};
+    if (hipError_t e = fs_set_max_lds_once((const void *)weighted_hist2d_kernel, lds_done); e != hipSuccess) return e;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int64_t want = (M + 3) / 4, cap = 2 * (int64_t)cus;  // the one sum whose order is free
+    const unsigned blocks = (unsigned)(want < cap ? want : cap);
+    hipLaunchKernelGGL(weighted_hist2d_kernel, dim3(blocks), dim3(256), (size_t)wh_lds_bytes(nb), st, cfg, M, N,
+                       half_box, edges2, nb, log_w, (const IwHeader *)state, hist);
     return hipGetLastError();
 }

@@ -603,6 +603,44 @@ int fs_sample_analysis(const float *z, int64_t M, int32_t N, double half_box, co
                   "fs_sample_analysis");
 }
 
+int64_t fs_iw_state_bytes(void) { return fs_iw_state_bytes_impl(); }
+
+int fs_iw_reset(void *state, void *stream) {
+    REQUIRE(state && ((uintptr_t)state & 7) == 0, "fs_iw_reset: state is NULL or not 8-byte aligned");
+    return hip_rc(fs_iw_reset_impl(state, (hipStream_t)stream), "fs_iw_reset");
+}
+
+int fs_importance_weights(double beta, int64_t M, const double *E, const float *log_q, double *log_w, void *state,
+                          void *stream) {
+    REQUIRE(M >= 0 && (M == 0 || (E && log_q && log_w && state)), "fs_importance_weights: invalid arguments");
+    REQUIRE(((uintptr_t)state & 7) == 0, "fs_importance_weights: state must be 8-byte aligned");
+    REQUIRE(beta > 0.0 && beta < INFINITY, "fs_importance_weights: beta must be positive and finite");
+    return hip_rc(fs_importance_weights_impl(beta, M, E, log_q, log_w, state, (hipStream_t)stream),
+                  "fs_importance_weights");
+}
+
+int fs_weighted_reduce(const int32_t *counts, int64_t M, int32_t r_nbins, const double *denom,
+                       const uint8_t *well_state, const double *avg_x, const double *log_w, const void *state,
+                       double *g_r_w, double *scalars, void *stream) {
+    REQUIRE(M >= 0 && (M == 0 || (counts && denom && well_state && avg_x && log_w && state && g_r_w && scalars)),
+            "fs_weighted_reduce: invalid arguments");
+    REQUIRE(r_nbins >= 1 && r_nbins <= 128, "fs_weighted_reduce: 1 <= r_nbins <= 128 (got %d)", r_nbins);
+    return hip_rc(fs_weighted_reduce_impl(counts, M, r_nbins, denom, well_state, avg_x, log_w, state, g_r_w, scalars,
+                                          (hipStream_t)stream),
+                  "fs_weighted_reduce");
+}
+
+int fs_weighted_hist2d(const float *samples, int64_t M, int32_t N, double half_box, const double *hist_edges,
+                       int32_t nbins, const double *log_w, const void *state, double *hist_w, void *stream) {
+    REQUIRE(hist_edges && M >= 0 && half_box > 0.0 && (M == 0 || (samples && log_w && state && hist_w)),
+            "fs_weighted_hist2d: invalid arguments");
+    REQUIRE(N >= 1 && N <= fs::kMaxN && nbins >= 1 && nbins <= 120,
+            "fs_weighted_hist2d: 1 <= N <= %d and 1 <= nbins <= 120 (got %d, %d)", fs::kMaxN, N, nbins);
+    return hip_rc(fs_weighted_hist2d_impl(samples, M, N, half_box, hist_edges, nbins, log_w, state, hist_w,
+                                          (hipStream_t)stream),
+                  "fs_weighted_hist2d");
+}
+
 }  // extern "C"
 
 int fs_linear_f32(int64_t M, int64_t N, int64_t K, const float *A, int64_t sam, int64_t sak, const float *B,

@@ -62,6 +62,16 @@ hipError_t fs_rdf_mean_impl(const int32_t *counts, int64_t M, int nb, const doub
 hipError_t fs_sample_analysis_impl(const float *z, int64_t M, int N, double half_box, const double *edges2, int nb,
                                    const double *edges_r, int nr, float *out, int64_t *hist, int32_t *counts,
                                    hipStream_t st);
+// importance weights of flow samples and the reweighted analysis (analysis_kernels.hip)
+int64_t fs_iw_state_bytes_impl();
+hipError_t fs_iw_reset_impl(void *state, hipStream_t st);
+hipError_t fs_importance_weights_impl(double beta, int64_t M, const double *E, const float *log_q, double *log_w,
+                                      void *state, hipStream_t st);
+hipError_t fs_weighted_reduce_impl(const int32_t *counts, int64_t M, int nr, const double *denom,
+                                   const uint8_t *wstate, const double *avg_x, const double *log_w, const void *state,
+                                   double *g_w, double *scalars, hipStream_t st);
+hipError_t fs_weighted_hist2d_impl(const float *cfg, int64_t M, int N, double half_box, const double *edges2, int nb,
+                                   const double *log_w, const void *state, double *hist, hipStream_t st);
 hipError_t fs_rqs_forward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
                                const float *ud, float B, float *out, float *lad, int32_t *nan_flag, hipStream_t st);
 hipError_t fs_rqs_backward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,

@@ -185,6 +185,12 @@ _SIGS = {
     "fs_rdf_mean": (ctypes.c_int, [_P, _I64, ctypes.c_int32, _P, _P, _P]),
     "fs_sample_analysis": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_double, _P, ctypes.c_int32, _P,
                                           ctypes.c_int32, _P, _P, _P, _P]),
+    "fs_iw_state_bytes": (_I64, []),
+    "fs_iw_reset": (ctypes.c_int, [_P, _P]),
+    "fs_importance_weights": (ctypes.c_int, [ctypes.c_double, _I64, _P, _P, _P, _P, _P]),
+    "fs_weighted_reduce": (ctypes.c_int, [_P, _I64, ctypes.c_int32] + [_P] * 7 + [_P]),
+    "fs_weighted_hist2d": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_double, _P, ctypes.c_int32, _P, _P, _P,
+                                           _P]),
     "fs_hist2d": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_double, _P, ctypes.c_int32, _P, _P]),
     "fs_well_stats": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P]),
 }

@@ -74,7 +74,7 @@ class Algorithm2:
     def __init__(self, bmc, model, batch_size=256, lr=0.000543510751759681, weight_decay=9.5857178422352e-05,
                  alpha=1.0, sampling_frequency=10, update_num_samples=1000, num_mc_runs=None, cumulative=False,
                  graphed=True, group=None, checkpoint_interval=None, num_samples_for_analysis=50000, out_dir=None,
-                 initial_p_acc=0.0, initial_training_num_samples=None, cmap_name=None):
+                 initial_p_acc=0.0, initial_training_num_samples=None, cmap_name=None, reweight_analysis=False):
         """bmc: this rank's BatchedMonteCarlo (its runs); model: the flow (the same
         initial weights on every rank); num_mc_runs: NUM_MC_RUNS over all ranks
         (default: bmc.C x world size).  Defaults are main_algorithm_2.py:32-64.
@@ -82,7 +82,12 @@ class Algorithm2:
         without it) with out_dir turns on run()'s checkpoint-cycle outputs:
         num_samples_for_analysis flow samples per analysis batch, initial_p_acc and
         initial_training_num_samples (INITIAL_TRAINING_NUM_SAMPLES, required) open
-        p_acc_history_data.json, cmap_name is stored in the heat-map JSON."""
+        p_acc_history_data.json, cmap_name is stored in the heat-map JSON.
+        reweight_analysis (not the reference's; default off: no new file): the analysis batch
+        also computes the importance weights of its samples against the engine's target
+        (analysis.sample_analysis(reweight=bmc.phys)) and writes
+        importance_cycle_{c}_data.json (io.write_importance); the chains and every other
+        file are those of a run without it."""
         self.bmc, self.model = bmc, model
         self.batch_size, self.lr, self.wd, self.alpha = int(batch_size), float(lr), float(weight_decay), float(alpha)
         self.sf = int(sampling_frequency)
@@ -106,6 +111,7 @@ class Algorithm2:
         self.initial_p_acc = initial_p_acc
         self.initial_training_num_samples = initial_training_num_samples
         self.cmap_name = cmap_name
+        self.reweight_analysis = bool(reweight_analysis)
         self.last_analysis = None  # the latest checkpoint cycle's analysis.sample_analysis result
         self._analysis_gen = None
         if self.checkpoint_interval is not None:
@@ -311,10 +317,13 @@ class Algorithm2:
             self._analysis_gen = torch.Generator(device=dev)
             self._analysis_gen.manual_seed((torch.initial_seed() + 1) % 2 ** 63)  # not the default stream's
         res = analysis.sample_analysis(self.model, self.num_samples_for_analysis, self.bmc.phys.half_width,
-                                       generator=self._analysis_gen)
+                                       generator=self._analysis_gen,
+                                       reweight=self.bmc.phys if self.reweight_analysis else None)
         io.save_samples(self.out_dir, res["samples"])
         io.write_frequency_heatmap(self.out_dir, c + 1, res["hist"], res["x_edges"], res["y_edges"], self.cmap_name)
         io.write_pair_correlation(self.out_dir, c + 1, res["r_vals"], res["g_r"])
+        if self.reweight_analysis:
+            io.write_importance(self.out_dir, c + 1, res)
         self.last_analysis = res
 
     def well_statistics(self, snapshots, start_idx, r0=1.2):

@@ -11,6 +11,9 @@ and the analysis batch of the Algorithm-2 driver's checkpoint cycles
 
   sample_analysis(model, n_samples, half_box, batch=1000, bins=100, dr=None)
 
+with, on request, the importance weights of those samples against the Boltzmann target
+(ESS, log Z, reweighted heat map, g(r) and well populations; sample_analysis(reweight=...)).
+
 Inputs are numpy arrays or device tensors; float32 and float64 inputs keep
 numpy's dtype semantics (the kernels reproduce numpy 2's weak-Python-float
 promotion).  The host side only does the per-configuration bookkeeping of the
@@ -139,7 +142,8 @@ def sample_analysis_batch(z, half_box, hist_edges, r_edges, samples_out, hist, c
                                               _lib.stream_ptr()), "fs_sample_analysis")
 
 
-def sample_analysis(model, n_samples, half_box, batch=1000, bins=100, dr=None, generator=None):
+def sample_analysis(model, n_samples, half_box, batch=1000, bins=100, dr=None, generator=None, reweight=None,
+                    density_pass=False, r0=1.2):
     """The analysis batch of an Algorithm-2 checkpoint cycle (main_algorithm_2.py:485-525)
     on the device: ceil(n_samples / batch) batches of model.sample(batch) in eval mode
     (all n_iterations * batch rows are kept, as the reference keeps them), each through
@@ -149,7 +153,23 @@ def sample_analysis(model, n_samples, half_box, batch=1000, bins=100, dr=None, g
     device's own), so the host generator that orders the training batches is untouched.
     Returns a dict: samples (n, N, 2) float32 device tensor (the rows of samples.npy),
     hist (nb, nb) int64, x_edges / y_edges (np.linspace(-bound, bound, bins)), r_vals,
-    g_r (numpy)."""
+    g_r (numpy).
+
+    reweight (a flowstate.MCMC.Physics whose box is 2 * half_box; default None: exactly the
+    analysis above): also the importance weights w = exp(-beta E(x)) / q(x) of the same
+    samples against that target and the analysis reweighted by them (include/flowstate.h
+    'Importance weights').  Per batch the sampling pass hands out its log-det, and one
+    energy launch, fs_classify_wells and fs_importance_weights follow fs_sample_analysis;
+    after the last batch fs_weighted_reduce and fs_weighted_hist2d run over all stored rows
+    with the final max_lw and S1 read on the device.  log q is the sampling pass's own
+    (log q0 - sum log|det|), or with density_pass=True the density pass over
+    fl32(config - half_width) exactly as BatchedMonteCarlo.proposal_terms derives it (one
+    more flow pass per batch).  r0: the well radius of classify_particles.  The keys above
+    are bit-identical to a call without reweight from the same generator state; added are
+    log_w (f64), log_q (f32), energy (f64) (n,) device tensors; ess, ess_fraction, log_z,
+    mean_log_w, max_weight_fraction (floats), n_zero, n_bad (ints); hist_w (nb, nb), g_r_w
+    (numpy float64), p_a_w, p_b_w, deltaF_w, avg_x_w (floats); and the unweighted p_a, p_b,
+    deltaF of the same samples (calculate_well_statistics' last values)."""
     half_box = float(half_box)
     if dr is None:
         dr = half_box / 50
@@ -157,6 +177,8 @@ def sample_analysis(model, n_samples, half_box, batch=1000, bins=100, dr=None, g
     N, dim = model.q0.n_particles, model.q0.n_dimension
     if dim != 2:
         raise ValueError("sample_analysis: two-dimensional particles only")
+    if reweight is not None and (float(reweight.half_width) != half_box or reweight.box_y != reweight.box_x):
+        raise ValueError("sample_analysis: reweight's box must be the square box of side 2 * half_box")
     n_iter = (int(n_samples) + batch - 1) // batch
     total = n_iter * batch
     x_edges = np.linspace(-half_box, half_box, bins)
@@ -174,19 +196,117 @@ def sample_analysis(model, n_samples, half_box, batch=1000, bins=100, dr=None, g
         counts = torch.empty((total, nr), dtype=torch.int32, device=dev)
         g = torch.empty(nr, dtype=torch.float64, device=dev)
         bound = float(model.q0.bound)
+        rw = None if reweight is None else _Reweighting(model, reweight, half_box, total, density_pass, r0, dev)
         for i in range(n_iter):
             u = torch.empty((batch, N * 2), dtype=torch.float32, device=dev).uniform_(-bound, bound,
                                                                                        generator=generator)
-            z = model.forward(u).reshape(batch, N, 2).contiguous()
-            sample_analysis_batch(z, half_box, e2, er, samples[i * batch:(i + 1) * batch], hist,
-                                  counts[i * batch:(i + 1) * batch])
+            rows = slice(i * batch, (i + 1) * batch)
+            if rw is None:
+                z = model.forward(u)
+            else:
+                z, log_det = model.forward_and_log_det(u)  # the same launch as forward()
+            z = z.reshape(batch, N, 2).contiguous()
+            sample_analysis_batch(z, half_box, e2, er, samples[rows], hist, counts[rows])
+            if rw is not None:
+                rw.batch(samples[rows], log_det, rows)
         if total:
             _lib.check(_lib.load().fs_rdf_mean(_lib.ptr(counts), total, nr, _lib.ptr(d), _lib.ptr(g),
                                                _lib.stream_ptr()), "fs_rdf_mean")
+        if rw is not None:
+            rw.finish(samples, counts, d, e2, nb)
     if was_training:
         model.train()
-    return {"samples": samples, "hist": hist, "x_edges": x_edges, "y_edges": x_edges.copy(), "r_vals": r_vals,
-            "g_r": g.cpu().numpy()}
+    res = {"samples": samples, "hist": hist, "x_edges": x_edges, "y_edges": x_edges.copy(), "r_vals": r_vals,
+           "g_r": g.cpu().numpy()}
+    if rw is not None:
+        res.update(rw.results())
+    return res
+
+
+def importance_summary(header):
+    """ess, ess_fraction, log_z, mean_log_w, max_weight_fraction, n_zero, n_bad from the seven
+    running statistics (max_lw, S1, S2, sum_lw, n, n_zero, n_bad) of an fs_importance_weights
+    state block, in float64 (include/flowstate.h 'Importance weights')."""
+    max_lw, s1, s2, sum_lw, n, n_zero, n_bad = header
+    s1, s2, n, n_zero, n_bad = float(s1), float(s2), int(n), int(n_zero), int(n_bad)
+    ess = s1 * s1 / s2 if s1 > 0 else 0.0
+    finite = n - n_zero - n_bad
+    return {"ess": ess, "ess_fraction": ess / n if n else 0.0,
+            "log_z": float(max_lw) + float(np.log(s1 / n)) if s1 > 0 else -np.inf,
+            "mean_log_w": float(sum_lw) / finite if finite else float("nan"),
+            "max_weight_fraction": 1.0 / s1 if s1 > 0 else float("nan"), "n_zero": n_zero, "n_bad": n_bad}
+
+
+def iw_state(device):
+    """A reset fs_importance_weights state block: int64 device tensor of fs_iw_state_bytes()
+    (words 0-3 hold the float64 max_lw, S1, S2, sum_lw; words 4-6 n, n_zero, n_bad)."""
+    L = _lib.load()
+    state = torch.empty(L.fs_iw_state_bytes() // 8, dtype=torch.int64, device=device)
+    _lib.check(L.fs_iw_reset(_lib.ptr(state), _lib.stream_ptr()), "fs_iw_reset")
+    return state
+
+
+def iw_header(state):
+    """(max_lw, S1, S2, sum_lw, n, n_zero, n_bad) of a state block, copied to the host."""
+    h = state[:8].cpu()
+    return tuple(h[:4].view(torch.float64).tolist()) + tuple(h[4:7].tolist())
+
+
+class _Reweighting:
+    """The importance-weight side of sample_analysis: per-row buffers, the state block and
+    the launches, all on the caller's stream with no host synchronisation before results()."""
+
+    def __init__(self, model, phys, half_box, total, density_pass, r0, dev):
+        self.model, self.phys, self.half_box, self.r0 = model, phys, half_box, float(r0)
+        self.N, self.total, self.density_pass = model.q0.n_particles, total, bool(density_pass)
+        model._base_check()
+        self.base = torch.tensor(model.q0.log_prob_constant(), dtype=torch.float32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.energy, self.log_w, self.avg_x = (torch.empty(total, **f64) for _ in range(3))
+        self.log_q = torch.empty(total, dtype=torch.float32, device=dev)
+        self.well = torch.empty(total, dtype=torch.uint8, device=dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.state = iw_state(dev)
+
+    def batch(self, cfg, log_det, rows):
+        L, p, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        M, N = cfg.shape[0], self.N
+        E, lq, lw = self.energy[rows], self.log_q[rows], self.log_w[rows]
+        _lib.check(L.fs_energy_lj_dw(self.phys.c, p(cfg), 1, M, N, p(E), None, None, None, st), "fs_energy_lj_dw")
+        _lib.check(L.fs_classify_wells(p(cfg), 1, M, N, self.half_box, self.r0, None, p(self.well[rows]),
+                                       p(self.avg_x[rows]), st), "fs_classify_wells")
+        if self.density_pass:  # BatchedMonteCarlo.proposal_terms' log q
+            x = (cfg.to(torch.float64) - self.phys.half_width).to(torch.float32).reshape(M, -1).contiguous()
+            lq.copy_(self.model._log_prob(x, self.err))
+        else:  # fs_flow_propose_lq's: fl32(log q0) - the sampling pass's summed log-dets, in float32
+            torch.sub(self.base, log_det, out=lq)
+        _lib.check(L.fs_importance_weights(float(self.phys.beta), M, p(E), p(lq), p(lw), p(self.state), st),
+                   "fs_importance_weights")
+
+    def finish(self, samples, counts, denom, edges2, nb):
+        L, p, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
+        dev, nr = samples.device, counts.shape[1]
+        self.g_w = torch.zeros(nr, dtype=torch.float64, device=dev)
+        self.scalars = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.hist_w = torch.zeros((nb, nb), dtype=torch.float64, device=dev)
+        _lib.check(L.fs_weighted_reduce(p(counts), self.total, nr, p(denom), p(self.well), p(self.avg_x),
+                                        p(self.log_w), p(self.state), p(self.g_w), p(self.scalars), st),
+                   "fs_weighted_reduce")
+        _lib.check(L.fs_weighted_hist2d(p(samples), self.total, self.N, self.half_box, p(edges2), nb, p(self.log_w),
+                                        p(self.state), p(self.hist_w), st), "fs_weighted_hist2d")
+
+    def results(self):
+        if int(self.err.item()) & 4:  # (density_pass) as BatchedMonteCarlo.check_errors
+            raise _lib.FlowStateError("a wide-path trunk hand-off timed out")
+        res = importance_summary(iw_header(self.state))
+        pa, pb, dF, ax = self.scalars.tolist()
+        well = self.well.cpu().numpy()
+        n = max(self.total, 1)
+        p_a, p_b = int((well == 1).sum()) / n, int((well == 2).sum()) / n
+        res.update(log_w=self.log_w, log_q=self.log_q, energy=self.energy, hist_w=self.hist_w.cpu().numpy(),
+                   g_r_w=self.g_w.cpu().numpy(), p_a_w=pa, p_b_w=pb, deltaF_w=dF, avg_x_w=ax, p_a=p_a, p_b=p_b,
+                   deltaF=float(np.log(p_b / p_a)) if (p_a > 0 and p_b > 0) else 0)
+        return res
 
 
 def generate_samples(model, n_particles, n_dimension, n_iterations=100, samples_per_iteration=5000,

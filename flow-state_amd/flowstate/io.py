@@ -17,6 +17,7 @@ and of the Algorithm-2 driver's checkpoint cycles (hybrid_NF_MCMC/main_algorithm
   loss_function_data.json                        utils.py:403-406
   model_checkpoint_cycle_{c}.pth                 main_algorithm_2.py:468-470
   p_acc_history_data.json                        main_algorithm_2.py:588-599
+  importance_cycle_{c}_data.json                 (not the reference's: Algorithm2(reweight_analysis=True))
 
 The batched engine returns sample() snapshots as device arrays (E, W and the
 configuration at each sampled step); `sample_tuples` turns one chain's snapshots
@@ -117,6 +118,23 @@ def write_pair_correlation(directory, cycle, r_vals, g_r):
     g = g_r.values if hasattr(g_r, "values") else g_r
     data = {"r": _tolist(r_vals), "g_r": _tolist(g), "directory": str(directory) + "/"}
     path = os.path.join(directory, f"pair_correlation_function_{cycle}_data.json")
+    with open(path, "w") as f:
+        json.dump(data, f)
+    return path
+
+
+IMPORTANCE_SCALARS = ("ess", "ess_fraction", "log_z", "mean_log_w", "max_weight_fraction", "n_zero", "n_bad", "p_a_w",
+                      "p_b_w", "deltaF_w", "avg_x_w", "p_a", "p_b", "deltaF")
+
+
+def write_importance(directory, cycle, res):
+    """importance_cycle_{cycle}_data.json: the importance-weight scalars of an analysis batch
+    (analysis.sample_analysis(reweight=...)), the reweighted g(r) over r and the reweighted
+    heat map (sum of the normalised weights per bin) with its edges."""
+    data = {k: res[k] for k in IMPORTANCE_SCALARS}
+    data.update(r=_tolist(res["r_vals"]), g_r_w=_tolist(res["g_r_w"]), hist_w=_tolist(res["hist_w"]),
+                x_edges=_tolist(res["x_edges"]), y_edges=_tolist(res["y_edges"]))
+    path = os.path.join(directory, f"importance_cycle_{cycle}_data.json")
     with open(path, "w") as f:
         json.dump(data, f)
     return path

@@ -789,6 +789,85 @@ int fs_sample_analysis(const float *z, int64_t M, int32_t N, double half_box, co
                        const double *r_edges, int32_t r_nbins, float *samples_out, int64_t *hist, int32_t *counts,
                        void *stream);
 
+/* ------------------------------------------------------------------ */
+/* Importance weights of flow samples against the Boltzmann target     */
+/* ------------------------------------------------------------------ */
+
+/* Definitions.  For a flow sample x (centred, float32):
+ *   config  = fl32(x + fl32(half_box))                  the rows of samples.npy
+ *   E       = fs_energy_lj_dw(config as float32)        float64, +inf on a hard-core overlap
+ *   log_q   float32: the sampling pass's own value log q0 - sum log|det| (what
+ *           fs_flow_propose_lq defines), or the density pass's
+ *           log_prob(fl32(config - half_width)) as nf_big_move derives it
+ *   lw      = (-beta) * E - (double)log_q               float64, one rounding per
+ *           operation, no contraction; w = exp(lw) = exp(-beta E) / q
+ *   zero-weight row: E = +inf gives lw = -inf, weight 0, counted in n_zero
+ *   bad row: NaN or +-inf log_q, or NaN or -inf E: lw = -inf, counted in n_bad
+ *           (checked first); a NaN never reaches a sum.
+ * Running statistics over all rows since the last fs_iw_reset:
+ *   max_lw; S1 = sum exp(lw - max_lw); S2 = sum exp(2 (lw - max_lw));
+ *   sum_lw over the rows with finite lw; n, n_zero, n_bad.
+ * The host derives from those seven numbers
+ *   ess = S1^2 / S2 (0 if S1 == 0), ess_fraction = ess / n,
+ *   log_z = max_lw + log(S1 / n), mean_log_w = sum_lw / (n - n_zero - n_bad),
+ *   max_weight_fraction = 1 / S1,
+ * and the normalised weight of row m is w~_m = exp(lw_m - max_lw) / S1.
+ *
+ * The state block is device memory, 8-byte aligned, fs_iw_state_bytes() long:
+ *   byte  0  double  max_lw   (-inf after a reset)
+ *         8  double  S1
+ *        16  double  S2
+ *        24  double  sum_lw
+ *        32  int64   n
+ *        40  int64   n_zero
+ *        48  int64   n_bad
+ *        56  int64   reserved (0)
+ *        64  1024 slots of 64 bytes, the per-workgroup partial sums of the batch in
+ *            flight {double max, S1, S2, sum_lw; int64 n_zero, n_bad, 0, 0}: scratch of
+ *            fs_importance_weights, meaningless between calls. */
+int64_t fs_iw_state_bytes(void);
+
+/* max_lw = -inf, every sum and count 0 (one stream-ordered launch). */
+int fs_iw_reset(void *state, void *stream);
+
+/* log_w[m] = lw of row m for E [M] f64 and log_q [M] f32, and the batch merged into
+ * the running statistics of `state` by the online log-sum-exp: when the batch raises
+ * max_lw, the old S1 and S2 are multiplied by exp(max_old - max_new) and its square.
+ * Two stream-ordered launches: per-workgroup partial sums, each shifted by the
+ * workgroup's own maximum, then one wave that rescales the partials to the new
+ * maximum and adds them in workgroup order.  The grid depends on M only
+ * (min(ceil(M / 256), 1024) workgroups) and no float atomics are used: the same rows
+ * in the same batches give the same bits on any device.  beta > 0.  A batch of only
+ * -inf rows leaves max_lw = -inf and S1 = 0.  M = 0 is a no-op. */
+int fs_importance_weights(double beta, int64_t M, const double *E, const float *log_q, double *log_w, void *state,
+                          void *stream);
+
+/* Reweighted g(r) and well statistics of M stored rows, with w~ from log_w [M] and the
+ * finished statistics in `state` (read on the device):
+ *   g_r_w[k]   = sum_m w~_m (counts[m][k] / denom[k])    counts [M][r_nbins] int32 of
+ *                fs_sample_analysis / fs_pair_hist, denom [r_nbins] as fs_rdf_mean's
+ *   scalars[0] = p_a_w = sum w~ [well_state == 1]         well_state [M], avg_x [M] of
+ *   scalars[1] = p_b_w = sum w~ [well_state == 2]         fs_classify_wells
+ *   scalars[2] = deltaF_w = ln(p_b_w / p_a_w), 0 if either is 0   (utils.py:92-96)
+ *   scalars[3] = avg_x_w = sum w~ avg_x
+ * Rows with lw = -inf are skipped; with S1 = 0 every output is 0.  The sums have a fixed
+ * order (thread t of a workgroup adds rows t, t + 256, ... in order, then a fixed tree
+ * over the 256 threads): bit-reproducible on any device.  r_nbins <= 128; M = 0 is a
+ * no-op. */
+int fs_weighted_reduce(const int32_t *counts, int64_t M, int32_t r_nbins, const double *denom,
+                       const uint8_t *well_state, const double *avg_x, const double *log_w, const void *state,
+                       double *g_r_w, double *scalars, void *stream);
+
+/* hist_w [nbins][nbins] f64 += sum_m w~_m * (number of particles of configuration m in
+ * the bin), for samples [M][N][2] float32 box coordinates (the rows of samples.npy):
+ * fs_sample_analysis's binning rule on (double)(sample - fl32(half_box)) against
+ * hist_edges [nbins+1], last edge inclusive.  Accumulated: the caller zeroes hist_w.
+ * Rows with lw = -inf are skipped.  The bins are summed with float64 atomic adds, so
+ * this is the one output whose summation order is free (last bits may differ from run
+ * to run).  N <= 64, nbins <= 120; M = 0 is a no-op. */
+int fs_weighted_hist2d(const float *samples, int64_t M, int32_t N, double half_box, const double *hist_edges,
+                       int32_t nbins, const double *log_w, const void *state, double *hist_w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
