@@ -583,6 +583,291 @@ __global__ void __launch_bounds__(256) weighted_hist2d_kernel(const float *__res
         if (h2[i] != 0.0) atomicAdd(&hist[i], h2[i]);
 }
 
+// ---------------------------------------------------------------------------------------
+// Chain diagnostics (flowstate.h, "Chain diagnostics"; not in the reference): a recorded
+// [T][C] series per observable of the batched engine's chains, and of those the per-chain
+// autocovariance, Sokal's windowed autocorrelation time, the pooled curve / R-hat terms and
+// the well hops.
+// ---------------------------------------------------------------------------------------
+
+__device__ inline bool finite_d(double v) { return fabs(v) < INFINITY; }  // false for NaN
+
+__device__ inline int wave_sum_int(int v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// every thread returns the sum over the 256 threads
+__device__ inline long long block_sum_i(long long v, long long *redi) {
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    v = wave_sum_i(v);
+    __syncthreads();
+    if (lane == 0) redi[wid] = v;
+    __syncthreads();
+    return redi[0] + redi[1] + redi[2] + redi[3];
+}
+
+// classify_kernel<T>'s classes and mean x of one chain whose values sit in float64 storage
+template <typename T>
+__device__ inline void observe_chain(const double *q, int N, int lane, double half_box, double r0, bool want_avg,
+                                     int &n_a, int &n_b, double &avg_x) {
+    const WellTest<T> w(half_box, r0);
+    int a = 0, b = 0;
+    for (int i = lane; i < N; i += 64) {
+        const int k = w.classify((T)q[2 * i], (T)q[2 * i + 1]);
+        a += k == 0;
+        b += k == 1;
+    }
+    n_a = wave_sum_int(a);
+    n_b = wave_sum_int(b);
+    if (want_avg && lane == 0) {
+        const T s = pairwise_sum_dev<T>([&](int64_t i) { return (T)q[2 * i]; }, N);
+        avg_x = (double)(s / (T)N);
+    }
+}
+
+// row t of the series from the engine's live arrays: well_stats_kernel's arrangement, one
+// wave per chain in that chain's reference dtype
+__global__ void __launch_bounds__(256) chain_observe_kernel(const double *__restrict__ pos,
+                                                            const uint8_t *__restrict__ is_f32,
+                                                            const double *__restrict__ E,
+                                                            const double *__restrict__ W,
+                                                            const uint8_t *__restrict__ accept, int64_t C, int N,
+                                                            double half_box, double r0, int64_t t, int64_t ld,
+                                                            fs_chain_series out) {
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * 4 + wid;
+    if (c >= C) return;
+    const int64_t row = t * ld + c;
+    if (out.avg_x || out.n_a || out.n_b) {
+        const double *q = pos + c * (int64_t)N * 2;
+        int n_a = 0, n_b = 0;
+        double avg_x = 0.0;
+        if (is_f32 && is_f32[c]) observe_chain<float>(q, N, lane, half_box, r0, out.avg_x != nullptr, n_a, n_b, avg_x);
+        else observe_chain<double>(q, N, lane, half_box, r0, out.avg_x != nullptr, n_a, n_b, avg_x);
+        if (lane == 0) {
+            if (out.avg_x) out.avg_x[row] = avg_x;
+            if (out.n_a) out.n_a[row] = (uint8_t)n_a;
+            if (out.n_b) out.n_b[row] = (uint8_t)n_b;
+        }
+    }
+    if (lane == 0) {
+        if (out.E) out.E[row] = E[c];
+        if (out.W) out.W[row] = W[c];
+        if (out.accept) out.accept[row] = accept[c];
+    }
+}
+
+// Per-chain mean and autocovariance.  A workgroup owns 64 chains (lane = chain: a row of the
+// series is one coalesced 512-byte read) and one block of kAcLagBlock lags; each of its 8
+// waves owns kAcR of those lags with their accumulators in registers for the whole series, so
+// the order of every (chain, lag) sum is the definition's whatever the tiling.  Per time tile
+// the workgroup stages the deviations d_t of the tile's rows and of the lag block's shifted
+// rows in LDS; a wave then reads d_t and ONE new shifted value per step and keeps the other
+// kAcR - 1 in a rotating register window (the step loop is unrolled kAcR times, so the window
+// is renamed, never moved).  Steps near the end of the series, where some of the wave's lags
+// have run out of rows, take the per-lag guarded loop.  Every wave sums the mean itself (the
+// same bits in each; the other seven hit the cache), so nothing is handed over.
+constexpr int kAcWaves = 8, kAcR = 16, kAcTile = 64;
+constexpr int kAcLagBlock = kAcWaves * kAcR;           // 128 lags per workgroup
+constexpr int kAcShRows = kAcTile + kAcLagBlock - 1;   // shifted rows a tile can touch
+constexpr int kAcLdsBytes = (kAcTile + kAcShRows) * 64 * 8;  // 130,560
+static_assert(kAcTile % kAcR == 0 && kAcLdsBytes <= 160 * 1024, "autocovariance tiling");
+
+template <typename X>
+__global__ void __launch_bounds__(kAcWaves * 64) chain_autocov_kernel(const X *__restrict__ x, int64_t T, int64_t C,
+                                                                      int64_t ld, int W, double *__restrict__ mean,
+                                                                      double *__restrict__ acov) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double *base = (double *)smem;        // [kAcTile][64]    d of rows t0 + r
+    double *sh = base + kAcTile * 64;     // [kAcShRows][64]  d of rows t0 + kb + r
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * 64 + lane;
+    const bool live = c < C;
+    const X *col = x + (live ? c : C - 1);  // idle lanes read the last chain and store nothing
+
+    const double x0 = (double)col[0];
+    double s = x0, mn = x0, mx = x0;  // min / max keep a NaN once seen
+#pragma unroll 8
+    for (int64_t t = 1; t < T; ++t) {
+        const double v = (double)col[t * ld];
+        s += v;
+        mn = (v < mn || v != v) ? v : mn;
+        mx = (v > mx || v != v) ? v : mx;
+    }
+    const bool constant = mn == mx;
+    const double m = constant ? x0 : s / (double)T;
+
+    const int kb = (int)blockIdx.y * kAcLagBlock, k0 = kb + wid * kAcR;
+    const bool active = k0 <= W;  // wave-uniform
+    double a[kAcR];
+#pragma unroll
+    for (int j = 0; j < kAcR; ++j) a[j] = 0.0;
+    const double *bp = base + lane, *sp = sh + wid * kAcR * 64 + lane;
+
+    for (int64_t t0 = 0; t0 < T - kb; t0 += kAcTile) {  // while the block's first lag has rows left
+        __syncthreads();
+        for (int r = wid; r < kAcTile; r += kAcWaves) {
+            const int64_t g = t0 + r;
+            base[r * 64 + lane] = g < T ? (double)col[g * ld] - m : 0.0;
+        }
+        for (int r = wid; r < kAcShRows; r += kAcWaves) {
+            const int64_t g = t0 + kb + r;
+            sh[r * 64 + lane] = g < T ? (double)col[g * ld] - m : 0.0;
+        }
+        __syncthreads();
+        if (!active) continue;
+        // step i of the tile has rows for lag k0 + j while i + j < lim
+        const int64_t lim = T - k0 - t0, limf = lim - (kAcR - 1);
+        const int nstep = lim >= kAcTile ? kAcTile : (lim > 0 ? (int)lim : 0);
+        const int nfast = limf >= kAcTile ? kAcTile : (limf > 0 ? (int)(limf / kAcR) * kAcR : 0);
+        if (nfast > 0) {
+            double w[kAcR];  // w[(u + j) % kAcR] = shifted row i + u + j at step i + u
+#pragma unroll
+            for (int j = 0; j < kAcR - 1; ++j) w[j] = sp[j * 64];
+            w[kAcR - 1] = 0.0;
+            for (int i = 0; i < nfast; i += kAcR) {
+#pragma unroll
+                for (int u = 0; u < kAcR; ++u) {
+                    w[(u + kAcR - 1) % kAcR] = sp[(i + u + kAcR - 1) * 64];
+                    const double d = bp[(i + u) * 64];
+#pragma unroll
+                    for (int j = 0; j < kAcR; ++j) {
+                        const double p = d * w[(u + j) % kAcR];
+                        a[j] += p;
+                    }
+                }
+            }
+        }
+        for (int i = nfast; i < nstep; ++i) {
+            const double d = bp[i * 64];
+#pragma unroll
+            for (int j = 0; j < kAcR; ++j)
+                if (i + j < lim) {
+                    const double p = d * sp[(i + j) * 64];
+                    a[j] += p;
+                }
+        }
+    }
+    if (!live) return;
+    if (blockIdx.y == 0 && wid == 0) mean[c] = m;
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < kAcR; ++j)
+            if (k0 + j <= W) acov[(int64_t)(k0 + j) * C + c] = constant ? 0.0 : a[j] / (double)T;
+    }
+}
+
+// Sokal's automatic window, one lane per chain
+__global__ void __launch_bounds__(256) chain_tau_kernel(const double *__restrict__ mean,
+                                                        const double *__restrict__ acov, int64_t C, int W,
+                                                        double c_window, double *__restrict__ tau,
+                                                        int32_t *__restrict__ window, uint8_t *__restrict__ flags) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const double v0 = acov[c];
+    double t = 0.0;
+    int win = 0;
+    uint8_t fl;
+    if (!finite_d(mean[c]) || !finite_d(v0)) fl = 4;
+    else if (v0 == 0.0) fl = 1;
+    else {
+        fl = 2;
+        win = W;
+        t = 0.5;
+        for (int k = 1; k <= W; ++k) {
+            t += acov[(int64_t)k * C + c] / v0;
+            if ((double)k >= c_window * t) {
+                win = k;
+                fl = 0;
+                break;
+            }
+        }
+    }
+    tau[c] = t;
+    window[c] = win;
+    flags[c] = fl;
+}
+
+// Across chains: workgroup k <= W the pooled autocovariance of lag k, workgroup W + 1 the
+// R-hat terms.  weighted_reduce_kernel's fixed order (thread t adds chains t, t + 256, .., then
+// block_sum's tree); chains with a non-finite mean or variance are skipped everywhere.
+__global__ void __launch_bounds__(256) chain_pool_kernel(const double *__restrict__ mean,
+                                                         const double *__restrict__ acov, int64_t C, int W,
+                                                         int64_t T, double *__restrict__ pooled,
+                                                         double *__restrict__ scalars) {
+    __shared__ double red[4];
+    __shared__ long long redi[4];
+    auto used = [&](int64_t c) { return finite_d(mean[c]) && finite_d(acov[c]); };
+    long long cnt = 0;
+    for (int64_t c = threadIdx.x; c < C; c += 256) cnt += used(c);
+    const long long n = block_sum_i(cnt, redi);
+    const double dn = (double)n;
+    const int k = blockIdx.x;
+    if (k <= W) {
+        double s = 0.0;
+        for (int64_t c = threadIdx.x; c < C; c += 256)
+            if (used(c)) s += acov[(int64_t)k * C + c];
+        s = block_sum(s, red);
+        if (threadIdx.x == 0) pooled[k] = n > 0 ? s / dn : 0.0;
+        return;
+    }
+    double sm = 0.0, sw = 0.0;
+    const double dT = (double)T, dT1 = (double)(T - 1);
+    for (int64_t c = threadIdx.x; c < C; c += 256)
+        if (used(c)) {
+            sm += mean[c];
+            if (T >= 2) sw += acov[c] * dT / dT1;
+        }
+    sm = block_sum(sm, red);
+    sw = block_sum(sw, red);
+    const double gm = n > 0 ? sm / dn : 0.0;
+    double sv = 0.0;
+    for (int64_t c = threadIdx.x; c < C; c += 256)
+        if (used(c)) {
+            const double d = mean[c] - gm;
+            sv += d * d;
+        }
+    sv = block_sum(sv, red);
+    if (threadIdx.x == 0) {
+        scalars[0] = gm;
+        scalars[1] = n >= 2 ? sv / (double)(n - 1) : 0.0;
+        scalars[2] = n > 0 ? sw / dn : 0.0;
+        scalars[3] = dn;
+    }
+}
+
+// calculate_well_statistics' all-in-A / all-in-B rule along time, one lane per chain
+__global__ void __launch_bounds__(256) chain_transitions_kernel(const uint8_t *__restrict__ n_a,
+                                                                const uint8_t *__restrict__ n_b, int64_t T, int64_t C,
+                                                                int64_t ld, int N, long long *__restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    long long steps[3] = {0, 0, 0}, ab = 0, ba = 0;  // steps: neither, A, B
+    int last = 0;
+#pragma unroll 4
+    for (int64_t t = 0; t < T; ++t) {
+        const int st = n_a[t * ld + c] == N ? 1 : (n_b[t * ld + c] == N ? 2 : 0);
+        steps[0] += st == 0;
+        steps[1] += st == 1;
+        steps[2] += st == 2;
+        if (st != 0) {
+            if (last != 0 && st != last) {
+                ab += st == 2;
+                ba += st == 1;
+            }
+            last = st;
+        }
+    }
+    long long *o = out + c * 6;
+    o[0] = steps[1];
+    o[1] = steps[2];
+    o[2] = steps[0];
+    o[3] = ab;
+    o[4] = ba;
+    o[5] = last;
+}
+
 }  // namespace fs
 
 using namespace fs;
@@ -683,5 +968,57 @@ hipError_t fs_weighted_hist2d_impl(const float *cfg, int64_t M, int N, double ha
     const unsigned blocks = (unsigned)(want < cap ? want : cap);
     hipLaunchKernelGGL(weighted_hist2d_kernel, dim3(blocks), dim3(256), (size_t)wh_lds_bytes(nb), st, cfg, M, N,
                        half_box, edges2, nb, log_w, (const IwHeader *)state, hist);
+    return hipGetLastError();
+}
+
+hipError_t fs_chain_observe_impl(const double *state, const uint8_t *is_f32, const double *E, const double *W,
+                                 const uint8_t *accept, int64_t C, int N, double half_box, double r0, int64_t t,
+                                 int64_t ld, const fs_chain_series *out, hipStream_t st) {
+    if (C <= 0) return hipSuccess;
+    hipLaunchKernelGGL(chain_observe_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, state, is_f32, E, W,
+                       accept, C, N, half_box, r0, t, ld, *out);
+    return hipGetLastError();
+}
+
+hipError_t fs_chain_autocov_impl(const void *x, int dtype, int64_t T, int64_t C, int64_t ld, int W, double *mean,
+                                 double *acov, hipStream_t st) {
+    if (C <= 0) return hipSuccess;
+    static std::atomic<unsigned long long> lds_f64{0}, lds_u8{0};
+    const dim3 grid((unsigned)((C + 63) / 64), (unsigned)(W / kAcLagBlock + 1));
+    if (dtype == 0) {
+        if (hipError_t e = fs_set_max_lds_once((const void *)chain_autocov_kernel<double>, lds_f64); e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(chain_autocov_kernel<double>, grid, dim3(kAcWaves * 64), (size_t)kAcLdsBytes, st,
+                           (const double *)x, T, C, ld, W, mean, acov);
+    } else {
+        if (hipError_t e = fs_set_max_lds_once((const void *)chain_autocov_kernel<uint8_t>, lds_u8); e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(chain_autocov_kernel<uint8_t>, grid, dim3(kAcWaves * 64), (size_t)kAcLdsBytes, st,
+                           (const uint8_t *)x, T, C, ld, W, mean, acov);
+    }
+    return hipGetLastError();
+}
+
+hipError_t fs_chain_tau_impl(const double *mean, const double *acov, int64_t C, int W, double c_window, double *tau,
+                             int32_t *window, uint8_t *flags, hipStream_t st) {
+    if (C <= 0) return hipSuccess;
+    hipLaunchKernelGGL(chain_tau_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, mean, acov, C, W,
+                       c_window, tau, window, flags);
+    return hipGetLastError();
+}
+
+hipError_t fs_chain_pool_impl(const double *mean, const double *acov, int64_t C, int W, int64_t T, double *pooled,
+                              double *scalars, hipStream_t st) {
+    if (C <= 0) return hipSuccess;
+    hipLaunchKernelGGL(chain_pool_kernel, dim3((unsigned)(W + 2)), dim3(256), 0, st, mean, acov, C, W, T, pooled,
+                       scalars);
+    return hipGetLastError();
+}
+
+hipError_t fs_chain_transitions_impl(const uint8_t *n_a, const uint8_t *n_b, int64_t T, int64_t C, int64_t ld, int N,
+                                     int64_t *out, hipStream_t st) {
+    if (C <= 0) return hipSuccess;
+    hipLaunchKernelGGL(chain_transitions_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, n_a, n_b, T, C,
+                       ld, N, (long long *)out);
     return hipGetLastError();
 }

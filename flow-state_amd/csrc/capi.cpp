@@ -641,6 +641,53 @@ int fs_weighted_hist2d(const float *samples, int64_t M, int32_t N, double half_b
                   "fs_weighted_hist2d");
 }
 
+int fs_chain_observe(const double *state, const uint8_t *state_is_f32, const double *E, const double *W,
+                     const uint8_t *accept, int64_t C, int32_t N, double half_box, double r0, int64_t t, int64_t ld,
+                     const fs_chain_series *out, void *stream) {
+    REQUIRE(out && C >= 0 && t >= 0 && ld >= C, "fs_chain_observe: needs out, C >= 0, t >= 0 and ld >= C");
+    REQUIRE(N >= 1 && N <= 255 && half_box > 0.0 && r0 > 0.0, "fs_chain_observe: 1 <= N <= 255 (got %d), half_box, r0 > 0",
+            N);
+    REQUIRE(C == 0 || ((state || !(out->avg_x || out->n_a || out->n_b)) && (E || !out->E) && (W || !out->W) &&
+                       (accept || !out->accept)),
+            "fs_chain_observe: a series is requested whose input array is NULL");
+    return hip_rc(fs_chain_observe_impl(state, state_is_f32, E, W, accept, C, N, half_box, r0, t, ld, out,
+                                        (hipStream_t)stream),
+                  "fs_chain_observe");
+}
+
+int fs_chain_autocov(const void *x, int32_t dtype, int64_t T, int64_t C, int64_t ld, int32_t W, double *mean,
+                     double *acov, void *stream) {
+    REQUIRE(T >= 1 && C >= 0 && ld >= C && (dtype == 0 || dtype == 1),
+            "fs_chain_autocov: needs T >= 1, C >= 0, ld >= C and dtype 0 (f64) or 1 (u8)");
+    REQUIRE(W >= 0 && W <= 512 && W <= T - 1, "fs_chain_autocov: 0 <= W <= min(T - 1, 512) (got W=%d, T=%lld)", W,
+            (long long)T);
+    REQUIRE(C == 0 || (x && mean && acov), "fs_chain_autocov: NULL array");
+    return hip_rc(fs_chain_autocov_impl(x, dtype, T, C, ld, W, mean, acov, (hipStream_t)stream), "fs_chain_autocov");
+}
+
+int fs_chain_tau(const double *mean, const double *acov, int64_t C, int32_t W, double c_window, double *tau,
+                 int32_t *window, uint8_t *flags, void *stream) {
+    REQUIRE(C >= 0 && W >= 0 && c_window > 0.0, "fs_chain_tau: needs C >= 0, W >= 0 and c_window > 0");
+    REQUIRE(C == 0 || (mean && acov && tau && window && flags), "fs_chain_tau: NULL array");
+    return hip_rc(fs_chain_tau_impl(mean, acov, C, W, c_window, tau, window, flags, (hipStream_t)stream),
+                  "fs_chain_tau");
+}
+
+int fs_chain_pool(const double *mean, const double *acov, int64_t C, int32_t W, int64_t T, double *pooled,
+                  double *scalars, void *stream) {
+    REQUIRE(C >= 0 && W >= 0 && T >= 1, "fs_chain_pool: needs C >= 0, W >= 0 and T >= 1");
+    REQUIRE(C == 0 || (mean && acov && pooled && scalars), "fs_chain_pool: NULL array");
+    return hip_rc(fs_chain_pool_impl(mean, acov, C, W, T, pooled, scalars, (hipStream_t)stream), "fs_chain_pool");
+}
+
+int fs_chain_transitions(const uint8_t *n_a, const uint8_t *n_b, int64_t T, int64_t C, int64_t ld, int32_t N,
+                         int64_t *out, void *stream) {
+    REQUIRE(T >= 0 && C >= 0 && ld >= C && N >= 1 && N <= 255,
+            "fs_chain_transitions: needs T >= 0, C >= 0, ld >= C and 1 <= N <= 255");
+    REQUIRE(C == 0 || (out && (T == 0 || (n_a && n_b))), "fs_chain_transitions: NULL array");
+    return hip_rc(fs_chain_transitions_impl(n_a, n_b, T, C, ld, N, out, (hipStream_t)stream), "fs_chain_transitions");
+}
+
 }  // extern "C"
 
 int fs_linear_f32(int64_t M, int64_t N, int64_t K, const float *A, int64_t sam, int64_t sak, const float *B,

@@ -72,6 +72,18 @@ hipError_t fs_weighted_reduce_impl(const int32_t *counts, int64_t M, int nr, con
                                    double *g_w, double *scalars, hipStream_t st);
 hipError_t fs_weighted_hist2d_impl(const float *cfg, int64_t M, int N, double half_box, const double *edges2, int nb,
                                    const double *log_w, const void *state, double *hist, hipStream_t st);
+// chain diagnostics: recorded series, autocovariance, tau, pooled terms, well hops (analysis_kernels.hip)
+hipError_t fs_chain_observe_impl(const double *state, const uint8_t *is_f32, const double *E, const double *W,
+                                 const uint8_t *accept, int64_t C, int N, double half_box, double r0, int64_t t,
+                                 int64_t ld, const fs_chain_series *out, hipStream_t st);
+hipError_t fs_chain_autocov_impl(const void *x, int dtype, int64_t T, int64_t C, int64_t ld, int W, double *mean,
+                                 double *acov, hipStream_t st);
+hipError_t fs_chain_tau_impl(const double *mean, const double *acov, int64_t C, int W, double c_window, double *tau,
+                             int32_t *window, uint8_t *flags, hipStream_t st);
+hipError_t fs_chain_pool_impl(const double *mean, const double *acov, int64_t C, int W, int64_t T, double *pooled,
+                              double *scalars, hipStream_t st);
+hipError_t fs_chain_transitions_impl(const uint8_t *n_a, const uint8_t *n_b, int64_t T, int64_t C, int64_t ld, int N,
+                                     int64_t *out, hipStream_t st);
 hipError_t fs_rqs_forward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
                                const float *ud, float B, float *out, float *lad, int32_t *nan_flag, hipStream_t st);
 hipError_t fs_rqs_backward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,

@@ -72,6 +72,11 @@ class BnFold(ctypes.Structure):
                 ("a_out", ctypes.c_void_p), ("B", ctypes.c_int64), ("H", ctypes.c_int32)]
 
 
+class ChainSeries(ctypes.Structure):
+    """fs_chain_series (include/flowstate.h): the series fs_chain_observe writes, each nullable."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("E", "W", "avg_x", "n_a", "n_b", "accept")]
+
+
 class FlowStateError(RuntimeError):
     pass
 
@@ -191,6 +196,12 @@ _SIGS = {
     "fs_weighted_reduce": (ctypes.c_int, [_P, _I64, ctypes.c_int32] + [_P] * 7 + [_P]),
     "fs_weighted_hist2d": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_double, _P, ctypes.c_int32, _P, _P, _P,
                                            _P]),
+    "fs_chain_observe": (ctypes.c_int, [_P] * 5 + [_I64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _I64, _I64,
+                                        ctypes.POINTER(ChainSeries), _P]),
+    "fs_chain_autocov": (ctypes.c_int, [_P, ctypes.c_int32, _I64, _I64, _I64, ctypes.c_int32, _P, _P, _P]),
+    "fs_chain_tau": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, ctypes.c_double, _P, _P, _P, _P]),
+    "fs_chain_pool": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _I64, _P, _P, _P]),
+    "fs_chain_transitions": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, ctypes.c_int32, _P, _P]),
     "fs_hist2d": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_double, _P, ctypes.c_int32, _P, _P]),
     "fs_well_stats": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, _P, _P]),
 }

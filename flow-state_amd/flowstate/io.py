@@ -18,6 +18,7 @@ and of the Algorithm-2 driver's checkpoint cycles (hybrid_NF_MCMC/main_algorithm
   model_checkpoint_cycle_{c}.pth                 main_algorithm_2.py:468-470
   p_acc_history_data.json                        main_algorithm_2.py:588-599
   importance_cycle_{c}_data.json                 (not the reference's: Algorithm2(reweight_analysis=True))
+  chain_diagnostics_data.json                    (not the reference's: diagnostics.diagnose)
 
 The batched engine returns sample() snapshots as device arrays (E, W and the
 configuration at each sampled step); `sample_tuples` turns one chain's snapshots
@@ -137,6 +138,16 @@ def write_importance(directory, cycle, res):
     path = os.path.join(directory, f"importance_cycle_{cycle}_data.json")
     with open(path, "w") as f:
         json.dump(data, f)
+    return path
+
+
+def write_chain_diagnostics(directory, result):
+    """chain_diagnostics_data.json: the summary of diagnostics.diagnose (plain floats, ints and
+    None: per observable the pooled tau and window, ess_total, rhat, the grand mean and the
+    counts of flagged chains; the mean pressure; the well-hop totals)."""
+    path = os.path.join(directory, "chain_diagnostics_data.json")
+    with open(path, "w") as f:
+        json.dump(result["summary"], f)
     return path
 
 

@@ -868,6 +868,102 @@ int fs_weighted_reduce(const int32_t *counts, int64_t M, int32_t r_nbins, const 
 int fs_weighted_hist2d(const float *samples, int64_t M, int32_t N, double half_box, const double *hist_edges,
                        int32_t nbins, const double *log_w, const void *state, double *hist_w, void *stream);
 
+/* ------------------------------------------------------------------ */
+/* Chain diagnostics                                                    */
+/* ------------------------------------------------------------------ */
+
+/* How well the batched engine's Markov chains mix (not in the reference, whose
+ * MonteCarlo.sample() only keeps a per-cycle history of E/N and pressure,
+ * monte_carlo.py:416-475): per-observable series recorded one row per step, and of a
+ * series the per-chain autocovariance, the integrated autocorrelation time, the terms
+ * of the Gelman-Rubin R-hat and the hops between the two wells.
+ * Conventions: every array is device memory.  A series is row-major [T][C], row = the
+ * recorded step, column = the chain, with a row stride of ld >= C elements.  Every
+ * entry point is stream-ordered, allocates nothing, never synchronises the host and is
+ * capture-safe; C = 0 is a no-op; bad arguments return FS_EINVAL with nothing launched. */
+
+/* The series fs_chain_observe writes; any pointer may be NULL (that series is skipped).
+ * E, W, avg_x float64; n_a, n_b, accept uint8. */
+typedef struct fs_chain_series {
+    double *E, *W, *avg_x;
+    uint8_t *n_a, *n_b, *accept;
+} fs_chain_series;
+
+/* Row t of the series from an engine's live arrays, one launch: state [C][N][2] f64,
+ * state_is_f32 [C] (nullable: all float64), E [C], W [C], accept [C] u8 (each needed only
+ * by the series of its name).
+ *   E[t][c], W[t][c], accept[t][c]   copies of the inputs
+ *   avg_x[t][c]   np.mean(config[:, 0])              } of chain c in its own dtype
+ *   n_a[t][c]     particles in the left well (class 0)  } (float32 where state_is_f32[c]),
+ *   n_b[t][c]     particles in the right well (class 1) } exactly fs_classify_wells' avg_x
+ *                 and cls of an array of that dtype holding the chain's values
+ * One wave per chain, as fs_well_stats.  Nothing but row t of the non-NULL series is
+ * written.  1 <= N <= 255 (the counts are bytes), t >= 0; the caller owns the rows. */
+int fs_chain_observe(const double *state, const uint8_t *state_is_f32, const double *E, const double *W,
+                     const uint8_t *accept, int64_t C, int32_t N, double half_box, double r0, int64_t t, int64_t ld,
+                     const fs_chain_series *out, void *stream);
+
+/* Per-chain mean and autocovariance at lags 0..W of the series x [T][C] (dtype 0:
+ * float64; 1: uint8, widened exactly to double): mean [C], acov [W+1][C] float64
+ * (contiguous).  T >= 1, 0 <= W <= min(T - 1, 512).  Every operation is rounded once, in
+ * this order, with no contraction:
+ *   s = x_0; s += x_t for t = 1..T-1; mean = s / T
+ *   the same pass tracks min and max (a NaN, once seen, stays).  If min == max the
+ *   series is constant: mean = x_0 and every acov[k] = +0 (a constant 0.1 would
+ *   otherwise leave a residual, and indicator series are often constant)
+ *   otherwise d_t = x_t - mean; a = 0; a += d_t * d_{t+k} for t = 0..T-1-k, the product
+ *   rounded before the add; acov[k] = a / T
+ * so the result does not depend on the launch shape.  A non-finite value anywhere in a
+ * chain's series makes that chain's mean and acov[0] non-finite (NaN or inf).
+ * 64 chains per workgroup (lane = chain), 128 lags per workgroup (grid.y blocks of
+ * lags), each wave 16 lags in registers; 130,560 bytes of LDS; no scratch, no atomics,
+ * nothing handed between workgroups. */
+int fs_chain_autocov(const void *x, int32_t dtype, int64_t T, int64_t C, int64_t ld, int32_t W, double *mean,
+                     double *acov, void *stream);
+
+/* Integrated autocorrelation time of each chain with Sokal's automatic window, from
+ * fs_chain_autocov's mean [C] and acov [W+1][C]; c_window > 0 (5 is customary).
+ * tau [C] f64, window [C] int32, flags [C] u8.  Checked in this order:
+ *   mean or acov[0] not finite   flags = 4 (NONFINITE), tau = 0, window = 0
+ *   acov[0] == 0                 flags = 1 (CONSTANT),  tau = 0, window = 0
+ *   otherwise tau(M) = 0.5 + sum_{k=1..M} (acov[k] / acov[0]), added in order of k;
+ *   window = the smallest M in 1..W with M >= c_window * tau(M), tau = tau(window),
+ *   flags = 0; if there is none (W = 0 included): window = W, tau = tau(W),
+ *   flags = 2 (TRUNCATED).
+ * One lane per chain.  With C = 1, mean = fs_chain_pool's scalars and acov = its pooled
+ * curve it gives the pooled tau. */
+int fs_chain_tau(const double *mean, const double *acov, int64_t C, int32_t W, double c_window, double *tau,
+                 int32_t *window, uint8_t *flags, void *stream);
+
+/* Across the chains, from fs_chain_autocov's mean and acov of series of length T.  Chains
+ * whose mean or acov[0] is not finite are skipped; constant chains count.  n_used is the
+ * number of chains left.
+ *   pooled[k]  = (sum_c acov[k][c]) / n_used, k = 0..W          pooled [W+1]
+ *   scalars[0] = (sum_c mean[c]) / n_used, the grand mean        scalars [4]
+ *   scalars[1] = sum_c (mean[c] - scalars[0])^2 / (n_used - 1)   (0 if n_used < 2), a
+ *                second pass inside the launch
+ *   scalars[2] = (sum_c (acov[0][c] * T) / (T - 1)) / n_used     (0 if T < 2)
+ *   scalars[3] = n_used
+ * and everything 0 when n_used = 0.  The host derives
+ *   rhat = sqrt((T - 1) / T + scalars[1] / scalars[2]),
+ * undefined when scalars[2] == 0 or n_used < 2.  One workgroup per lag plus one for the
+ * scalars; the order of every sum is fixed as in fs_weighted_reduce (thread t adds
+ * chains t, t + 256, ... in order, then a fixed tree over the 256 threads): no float
+ * atomics, bit-reproducible on any device. */
+int fs_chain_pool(const double *mean, const double *acov, int64_t C, int32_t W, int64_t T, double *pooled,
+                  double *scalars, void *stream);
+
+/* Well hops along time from the series n_a, n_b [T][C] u8 of fs_chain_observe, by
+ * calculate_well_statistics' all-in-A / all-in-B rule (utils.py:61-101):
+ *   s_t = 1 if n_a == N, else 2 if n_b == N, else 0
+ *   last = 0; at each s_t != 0: if last != 0 and s_t != last, one A->B hop (s_t = 2) or
+ *   one B->A hop (s_t = 1); then last = s_t
+ * so an excursion A -> neither -> A is no hop and A -> neither -> B is one.
+ * out [C][6] int64 (overwritten) = {steps_A, steps_B, steps_neither, hops_AB, hops_BA,
+ * last}.  One lane per chain, sequential over t.  1 <= N <= 255; T = 0 gives zeros. */
+int fs_chain_transitions(const uint8_t *n_a, const uint8_t *n_b, int64_t T, int64_t C, int64_t ld, int32_t N,
+                         int64_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
