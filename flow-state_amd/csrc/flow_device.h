@@ -180,7 +180,21 @@ __device__ __forceinline__ void rqs_eval(float x, float icw, float ibw, float ic
         const float c = -idl * xm;
         const float disc = fabsf(b * b - (4.f * a) * c);
         nan_disc = disc != disc;
-        const float root = (2.f * c) / (-b - sqrtf(disc));
+        // The reference takes 2 c / (-b - sqrt(disc)) whatever the sign of b.  With b < 0 (a flat
+        // bin between larger end derivatives, towards its top) -b and sqrt(disc) nearly agree
+        // and their difference loses up to ~1e3 x its rounding: the root is then off by ~1e-5,
+        // (1 - root) by several percent and the log-det by ~0.1 (the reference's own float32
+        // error there).  The same root in its other form, (-b + sqrt(disc)) / (2 a), has no
+        // cancellation for b < 0; for b >= 0 the reference's form is the stable one.
+        const float sq = sqrtf(disc);
+        float root = b >= 0.f ? (2.f * c) / (-b - sq) : (sq - b) / (2.f * a);
+        // The exact root lies in [0, 1].  In a steep bin (idl >> d0, d1) b * b - 4 a c itself
+        // cancels nearly all of its bits towards the bin's top, so the float32 root can exceed
+        // 1 by ~1e-4; 2 idl root (1 - root) < -d1 then makes dnum negative and the log-det NaN
+        // (the reference does not pin the root: its float32 returns that NaN, and raises only on
+        // a NaN discriminant).  Pinned to the bin, both logarithms take positive arguments; a
+        // NaN root stays NaN.
+        root = root > 1.f ? 1.f : (root < 0.f ? 0.f : root);
         y = root * ibw + icw;
         const float tomt = root * (1.f - root);
         const float den = idl + sdd * tomt;
