@@ -167,6 +167,35 @@ __device__ __forceinline__ void knots_from_logits(const float (&u)[K], float (&k
     kn[K] = a.B;
 }
 
+// searchsorted (splines.py:11-13) over the bins of w[0..NB] as a bisection that carries the
+// knots along: each level compares x with the middle knot and keeps the half it falls in
+// (one select per surviving knot; the shorter half is padded with its top knot, which x is
+// then below, so a padded bin is never entered), down to the bin's two knots k0, k1.  The
+// interior knots are non-decreasing (knots_from_logits: a cumsum of positive terms, rounded
+// once) or all NaN, so this is the last k with x >= w[k], the bin a linear scan finds: ties
+// go right, the end knots are never compared (x below -B: bin 0, x at +B: the last bin),
+// and a NaN x or NaN knots fail every compare (bin 0).  SEARCH = false replays the recorded
+// path c[] on another knot set: that set's knots bin, bin + 1.  36 selects per knot set at
+// 32 bins, against a scan's 4 (searched) and 3 (replayed) instructions per knot.
+template <int NB, bool SEARCH>
+__device__ __forceinline__ void knot_bisect(const float (&w)[NB + 1], float x, bool (&c)[8], int lvl, int &bin,
+                                            float &k0, float &k1) {
+    if constexpr (NB == 1) {
+        k0 = w[0];
+        k1 = w[1];
+    } else {
+        constexpr int MID = NB / 2, NN = NB - MID;
+        if (SEARCH) {
+            c[lvl] = x >= w[MID];
+            bin += c[lvl] ? MID : 0;
+        }
+        float v[NN + 1];
+#pragma unroll
+        for (int i = 0; i <= NN; ++i) v[i] = c[lvl] ? w[MID + i] : w[i < MID ? i : MID];
+        knot_bisect<NN, SEARCH>(v, x, c, lvl + 1, bin, k0, k1);
+    }
+}
+
 // rational_quadratic_spline forward (splines.py:202-222) / inverse (:162-201)
 template <bool INV>
 __device__ __forceinline__ void rqs_eval(float x, float icw, float ibw, float ich, float ih, float d0,

@@ -155,39 +155,73 @@ __device__ __forceinline__ void gemm64(const float *__restrict__ X, __amdgpu_buf
     gemm_run<XS, RT, CT, PD, ACC, TR>(X, W, sec, kg, rt0, ct0, br, acc);
 }
 
-// Transposed final-layer tile of both chain halves with the column biases preset in the
-// accumulators (register i of lane half h = column 8 (i >> 2) + 4 h + (i & 3)), turned
-// lane-per-chain by 16 v_permlane32_swap: row k of the result is tile_row(t[0][0], t[1][0], k).
-template <int XS, int FPD = 4>
-__device__ __forceinline__ void final_tile(const float *__restrict__ X, __amdgpu_buffer_rsrc_t W, int sec, int kg,
-                                           int tile, const float *__restrict__ b, f32x16 (&t)[2][1]) {
-    const int h = (threadIdx.x >> 5) & 1;
+// What a transposed final-layer tile needs that does not depend on the activations: its
+// column biases, the preset of both row tiles' accumulators (register i of lane half h =
+// column 8 (i >> 2) + 4 h + (i & 3)), and its first FPD weight fragments.  final_issue()
+// requests the biases and the first NS fragments, final_gemm() the rest and runs the GEMM; a
+// caller with vector work ahead of the GEMM issues first, so the L2 round trip of both
+// runs under that work instead of in front of the tile's first MFMA (the ResNet GEMMs do
+// the same across their barriers).  With one fragment ahead the first k-group's 8 MFMAs
+// cover the others' latency; NS < FPD is for where the registers are short.
+template <int FPD>
+struct FinalPre {
+    BRing<1, FPD> br;
+    f32x16 b;
+};
+
+template <int FPD, int S0, int S1>
+__device__ __forceinline__ void final_frags(BRing<1, FPD> &br, __amdgpu_buffer_rsrc_t W, int sec, int kg, int tile) {
+    const int voff = (tile * kg * 64 + (int)(threadIdx.x & 63)) * 16;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 v = *(const f32x4 *)(b + 8 * g + 4 * h);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) t[0][0][4 * g + j] = t[1][0][4 * g + j] = v[j];
-    }
-    gemm64<XS, 2, 1, FPD, true, true>(X, W, sec, kg, 0, tile, t);
-    lanes_to_chains(t[0][0], t[1][0]);
+    for (int s = S0; s < S1; ++s)
+        if (s < kg) br.rb[s][0] = ldb_frag(W, voff, sec + s * 1024);
 }
 
-// The same for K <= 16 with two transform features per tile: feature 2p in columns
-// 0..15, feature 2p+1 in 16..31 (ba, bb: their bias rows), so the widths / heights GEMMs
-// of a pair cost one tile each instead of two half-empty ones.
-template <int XS, int FPD = 4>
-__device__ __forceinline__ void final_tile_pair(const float *__restrict__ X, __amdgpu_buffer_rsrc_t W, int sec,
-                                                int kg, int tile, const float *__restrict__ ba,
-                                                const float *__restrict__ bb, f32x16 (&t)[2][1]) {
+// ba: bias row of columns 0..15, bb: of columns 16..31 (one feature's 32 columns: bb = ba +
+// 16; a feature pair for K <= 16: the two features' rows)
+template <int FPD, int NS = FPD>
+__device__ __forceinline__ void final_issue(__amdgpu_buffer_rsrc_t W, int sec, int kg, int tile,
+                                            const float *__restrict__ ba, const float *__restrict__ bb,
+                                            FinalPre<FPD> &p) {
     const int h = (threadIdx.x >> 5) & 1;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const f32x4 v = *(const f32x4 *)((g < 2 ? ba + 8 * g : bb + 8 * (g - 2)) + 4 * h);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) t[0][0][4 * g + j] = t[1][0][4 * g + j] = v[j];
+        for (int j = 0; j < 4; ++j) p.b[4 * g + j] = v[j];
     }
-    gemm64<XS, 2, 1, FPD, true, true>(X, W, sec, kg, 0, tile, t);
+    final_frags<FPD, 0, NS>(p.br, W, sec, kg, tile);
+}
+
+// The tile of both chain halves from its operands, of which final_issue<FPD, NS> has
+// requested the first NS fragments
+template <int XS, int FPD, int NS = FPD>
+__device__ __forceinline__ void final_gemm(const float *__restrict__ X, __amdgpu_buffer_rsrc_t W, int sec, int kg,
+                                           int tile, FinalPre<FPD> &p, f32x16 (&t)[2][1]) {
+    final_frags<FPD, NS, FPD>(p.br, W, sec, kg, tile);
+    t[0][0] = t[1][0] = p.b;
+    gemm_run<XS, 2, 1, FPD, true, true>(X, W, sec, kg, 0, tile, p.br, t);
+}
+
+// ... turned lane-per-chain by 16 v_permlane32_swap: row k of the result is
+// tile_row(t[0][0], t[1][0], k)
+template <int XS, int FPD, int NS = FPD>
+__device__ __forceinline__ void final_run(const float *__restrict__ X, __amdgpu_buffer_rsrc_t W, int sec, int kg,
+                                          int tile, FinalPre<FPD> &p, f32x16 (&t)[2][1]) {
+    final_gemm<XS, FPD, NS>(X, W, sec, kg, tile, p, t);
     lanes_to_chains(t[0][0], t[1][0]);
+}
+
+// Issue and run in one go, for K <= 16 with two transform features per tile: feature 2p in
+// columns 0..15, feature 2p+1 in 16..31 (ba, bb: their bias rows), so the widths / heights
+// GEMMs of a pair cost one tile each instead of two half-empty ones.
+template <int XS, int FPD = 4>
+__device__ __forceinline__ void final_tile_pair(const float *__restrict__ X, __amdgpu_buffer_rsrc_t W, int sec,
+                                                int kg, int tile, const float *__restrict__ ba,
+                                                const float *__restrict__ bb, f32x16 (&t)[2][1]) {
+    FinalPre<FPD> p;
+    final_issue<FPD>(W, sec, kg, tile, ba, bb, p);
+    final_run<XS, FPD>(X, W, sec, kg, tile, p, t);
 }
 
 // final_tile_pair for the 32 chains of X's first row tile, duplicated into both lane halves
@@ -271,40 +305,50 @@ __device__ __forceinline__ void drows_dot(const DRows<QB> &g, const float *xr, i
 // d_K tail GEMM: 9 % of the pass's MFMA work.  The bin comes from the knots of the
 // searched tile (cumwidths in the density direction, cumheights when inverting), so
 // that tile runs first and the first gathers are in flight during the other tile's GEMM.
+// pre: the searched tile's operands, issued by the caller (or by the previous feature's
+// call); bfn: the bias rows of the feature this wave takes next, or null.  Each tile's
+// operands are requested right after the GEMM before it, ahead of that tile's knots: the
+// other tile's after the searched GEMM, the next feature's searched tile's (left in pre)
+// after the other GEMM, so every GEMM here starts on operands that landed under a vector
+// section.  (Not just before the dot-product loop: its first wait, merged over the
+// iterations, would then wait for loads issued a moment earlier.)  The next feature's
+// operands wait over the other tile's knots, where the first gather batch is live too
+// and the 256 registers are short: kNextFrags of its weight fragments go ahead (2 spill in
+// flow_pass_kernel<256, 32, *>, 4 spill more), the rest follows at its GEMM.
+constexpr int kNextFrags = 1;
+
 template <int XS, int H, int K, bool INV, int FPD = 4>
 __device__ __forceinline__ float cond_spline(const float *__restrict__ X, __amdgpu_buffer_rsrc_t W, int sec,
                                              int kg, const float *__restrict__ bf, int dsec,
                                              const float *__restrict__ bd, float *CO, int cs, int p, int j,
-                                             const FlowArgs &a, bool &nan_any, Prof &pf) {
+                                             const FlowArgs &a, bool &nan_any, Prof &pf, FinalPre<FPD> &pre,
+                                             const float *__restrict__ bfn, int jn) {
     constexpr int NQ = H / 4;                   // quads of the hidden vector
     constexpr int QB = NQ >= 8 ? 4 : NQ / 2;    // quads per gather batch
     const int lane = threadIdx.x & 63;
     const float x = CO[lane * cs + p];
     const bool inside = (x >= a.negB) && (x <= a.B);
     constexpr int TS = INV ? 1 : 0;  // searched tile: 0 widths, 1 heights
+    FinalPre<FPD> po;
     float ks[K + 1];
     {
         f32x16 acc[2][1];
-        final_tile<XS, FPD>(X, W, sec, kg, 2 * j + TS, bf + 32 * TS, acc);
+        final_gemm<XS, FPD, kNextFrags>(X, W, sec, kg, 2 * j + TS, pre, acc);
+        final_issue<FPD>(W, sec, kg, 2 * j + 1 - TS, bf + 32 * (1 - TS), bf + 32 * (1 - TS) + 16, po);
+        __builtin_amdgcn_sched_barrier(0);
+        lanes_to_chains(acc[0][0], acc[1][0]);
         pf.mark(PH_FINAL_GEMM);
         float u[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) u[k] = tile_row(acc[0][0], acc[1][0], k);
         knots_from_logits<K>(u, ks, INV ? kMinHd : kMinWd, a);
     }
-    // searchsorted (splines.py:11-13): knots are non-decreasing, so the last k
-    // with x >= knot[k] is the bin; the gathered knots ride along the scan
+    // searchsorted (splines.py:11-13); the bin's two knots come out of the search
     // (register-resident, no dynamically indexed array)
     int bin = 0;
-    float s0 = ks[0], s1 = ks[1];
-#pragma unroll
-    for (int k = 1; k < K; ++k) {
-        if (x >= ks[k]) {
-            bin = k;
-            s0 = ks[k];
-            s1 = ks[k + 1];
-        }
-    }
+    bool path[8];
+    float s0, s1;
+    knot_bisect<K, true>(ks, x, path, 0, bin, s0, s1);
     // d_bin, d_bin+1 = bias + row . h  (bin + 1 <= K: row K is the circular-tail d_K)
     const int voff = bin * 16;
     DRows<QB> g0, g1;
@@ -314,21 +358,18 @@ __device__ __forceinline__ float cond_spline(const float *__restrict__ X, __amdg
     float o0, o1;
     {
         f32x16 acc[2][1];
-        final_tile<XS, FPD>(X, W, sec, kg, 2 * j + 1 - TS, bf + 32 * (1 - TS), acc);
+        final_gemm<XS, FPD>(X, W, sec, kg, 2 * j + 1 - TS, po, acc);
+        if (bfn) {
+            final_issue<FPD, kNextFrags>(W, sec, kg, 2 * jn + TS, bfn + 32 * TS, bfn + 32 * TS + 16, pre);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        lanes_to_chains(acc[0][0], acc[1][0]);
         pf.mark(PH_FINAL_GEMM);
         float u[K], ko[K + 1];
 #pragma unroll
         for (int k = 0; k < K; ++k) u[k] = tile_row(acc[0][0], acc[1][0], k);
         knots_from_logits<K>(u, ko, INV ? kMinWd : kMinHd, a);
-        o0 = ko[0];
-        o1 = ko[1];
-#pragma unroll
-        for (int k = 1; k < K; ++k) {
-            if (k == bin) {
-                o0 = ko[k];
-                o1 = ko[k + 1];
-            }
-        }
+        knot_bisect<K, false>(ko, x, path, 0, bin, o0, o1);
     }
     pf.mark(PH_SPLINE);
     const float *xr = X + lane * XS;
@@ -372,15 +413,9 @@ __device__ __forceinline__ float spline_from_logits(const float (&uS)[K], const 
     float ks[K + 1];
     knots_from_logits<K>(uS, ks, INV ? kMinHd : kMinWd, a);
     int bin = 0;
-    float s0 = ks[0], s1 = ks[1];
-#pragma unroll
-    for (int k = 1; k < K; ++k) {
-        if (x >= ks[k]) {
-            bin = k;
-            s0 = ks[k];
-            s1 = ks[k + 1];
-        }
-    }
+    bool path[8];
+    float s0, s1;
+    knot_bisect<K, true>(ks, x, path, 0, bin, s0, s1);
     const int voff = bin * 16;
     DRows<QB> g0, g1;
     drows_issue<QB, K>(g0, W, voff, dsec, 0);
@@ -389,15 +424,7 @@ __device__ __forceinline__ float spline_from_logits(const float (&uS)[K], const 
     {
         float ko[K + 1];
         knots_from_logits<K>(uO, ko, INV ? kMinWd : kMinHd, a);
-        o0 = ko[0];
-        o1 = ko[1];
-#pragma unroll
-        for (int k = 1; k < K; ++k) {
-            if (k == bin) {
-                o0 = ko[k];
-                o1 = ko[k + 1];
-            }
-        }
+        knot_bisect<K, false>(ko, x, path, 0, bin, o0, o1);
     }
     pf.mark(PH_SPLINE);
 #pragma unroll 1
@@ -624,21 +651,39 @@ __global__ void __launch_bounds__(kThreads, 2) flow_pass_kernel(FlowArgs a) {
             }
         }
         pf.mark(PH_EPI);
+        // final layer + conditional spline, feature by feature (K <= 16: feature pairs share
+        // the widths / heights tiles).  K > 16: the first searched tile's biases and weight
+        // fragments are requested before the barrier, as the ResNet GEMMs' are.
+        constexpr bool INV = MODE != MODE_DENSITY;
+        constexpr int TS = INV ? 1 : 0;
+        const int wfsec = (int)(PL.wf * 4);
+        const float *BF = V + PL.v_bf;
+        FinalPre<4> fpre;
+        if constexpr (K > 16) {
+            if (wid < N) {
+                final_issue<4, kNextFrags>(W, wfsec, PL.kg_h, 2 * wid + TS, BF + 96 * wid + 32 * TS,
+                                           BF + 96 * wid + 32 * TS + 16, fpre);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
         __syncthreads();
         pf.mark(PH_BARRIER);
-        // final layer + conditional spline, feature by feature
-        if constexpr (K <= 16) {  // feature pairs share the widths / heights tiles
-            constexpr bool INV = MODE != MODE_DENSITY;
-            constexpr int TS = INV ? 1 : 0;
+        if constexpr (K <= 16) {
             for (int pp = wid; pp < (N + 1) / 2; pp += kWaves) {
                 const int ja = 2 * pp, jb = 2 * pp + 1;
                 const bool hb = jb < N;
-                const float *ba = V + PL.v_bf + 96 * ja;
-                const float *bb = hb ? V + PL.v_bf + 96 * jb : ba + 16;  // zeros beyond K
+                const float *ba = BF + 96 * ja;
+                const float *bb = hb ? BF + 96 * jb : ba + 16;  // zeros beyond K
+                // both tiles' operands requested at once: the other tile's land under the
+                // searched tile's GEMM.  (Nothing is carried over the pair's splines, which
+                // hold both tiles: no registers to spare there.)
+                FinalPre<4> fo;
+                final_issue<4>(W, wfsec, PL.kg_h, 2 * pp + TS, ba + 32 * TS, bb + 32 * TS, fpre);
+                final_issue<4>(W, wfsec, PL.kg_h, 2 * pp + 1 - TS, ba + 32 * (1 - TS), bb + 32 * (1 - TS), fo);
+                __builtin_amdgcn_sched_barrier(0);
                 f32x16 tS[2][1], tO[2][1];
-                final_tile_pair<XS>(X, W, (int)(PL.wf * 4), PL.kg_h, 2 * pp + TS, ba + 32 * TS, bb + 32 * TS, tS);
-                final_tile_pair<XS>(X, W, (int)(PL.wf * 4), PL.kg_h, 2 * pp + 1 - TS, ba + 32 * (1 - TS),
-                                    bb + 32 * (1 - TS), tO);
+                final_run<XS, 4>(X, W, wfsec, PL.kg_h, 2 * pp + TS, fpre, tS);
+                final_run<XS, 4>(X, W, wfsec, PL.kg_h, 2 * pp + 1 - TS, fo, tO);
                 pf.mark(PH_FINAL_GEMM);
                 ld += spline_from_tiles<XS, H, K, INV>(tS, tO, 0, X, W, (int)((PL.wd + (int64_t)ja * H * (K + 1)) * 4),
                                                        V + PL.v_bd + ja * (K + 1), CO, cs, (2 * ja + 1 + off) % D, a,
@@ -650,12 +695,13 @@ __global__ void __launch_bounds__(kThreads, 2) flow_pass_kernel(FlowArgs a) {
                                                            a, nan_any, pf);
             }
         } else {
-        for (int j = wid; j < N; j += kWaves) {
-            const int p = (2 * j + 1 + off) % D;
-            ld += cond_spline<XS, H, K, MODE != MODE_DENSITY>(
-                X, W, (int)(PL.wf * 4), PL.kg_h, V + PL.v_bf + 96 * j, (int)((PL.wd + (int64_t)j * H * (K + 1)) * 4),
-                V + PL.v_bd + j * (K + 1), CO, cs, p, j, a, nan_any, pf);
-        }
+            for (int j = wid; j < N; j += kWaves) {
+                const int p = (2 * j + 1 + off) % D, jn = j + kWaves;
+                ld += cond_spline<XS, H, K, INV>(X, W, wfsec, PL.kg_h, BF + 96 * j,
+                                                 (int)((PL.wd + (int64_t)j * H * (K + 1)) * 4),
+                                                 V + PL.v_bd + j * (K + 1), CO, cs, p, j, a, nan_any, pf, fpre,
+                                                 jn < N ? BF + 96 * jn : nullptr, jn);
+            }
         }
         if (MODE == MODE_DENSITY) {
             ld += uncond_spline<K, false>(P + PL.unc, CO, cs, N, D, off, a, nan_any);
@@ -1647,9 +1693,14 @@ __global__ void __launch_bounds__(64 * WPB) wide_final_kernel(WideArgs w) {
         }
     } else if constexpr (RB == kRows) {
         const int j = u;
+        constexpr int TS = MODE != MODE_DENSITY ? 1 : 0;
+        const float *bf = V + PL.v_bf + 96 * j;
+        FinalPre<kWideFPD> pre;
+        final_issue<kWideFPD, kNextFrags>(W, (int)(PL.wf * 4), PL.kg_h, 2 * j + TS, bf + 32 * TS, bf + 32 * TS + 16,
+                                          pre);
         lc[j] = cond_spline<XS, H, K, MODE != MODE_DENSITY, kWideFPD>(
-            X, W, (int)(PL.wf * 4), PL.kg_h, V + PL.v_bf + 96 * j, (int)((PL.wd + (int64_t)j * H * (K + 1)) * 4),
-            V + PL.v_bd + j * (K + 1), CO, cs, (2 * j + 1 + off) % D, j, a, nan_any, pf);
+            X, W, (int)(PL.wf * 4), PL.kg_h, bf, (int)((PL.wd + (int64_t)j * H * (K + 1)) * 4),
+            V + PL.v_bd + j * (K + 1), CO, cs, (2 * j + 1 + off) % D, j, a, nan_any, pf, pre, nullptr, -1);
     } else {  // K > 16 on 32-row blocks: cond_spline's tiles and spline, split as for the pairs
         constexpr bool INV = MODE != MODE_DENSITY;
         constexpr int TS = INV ? 1 : 0;
