@@ -14,6 +14,11 @@
 // the knot values through -F_q / F_theta (implicit function theorem).  Knot adjoints go
 // back through the pinned cumsum (suffix sums), the min-width affine and softmax;
 // derivative adjoints through softplus (threshold 20, as torch).
+//
+// There is one spline family.  The arithmetic of an element in its bin (rqs_bin_theta, rqs_bin,
+// rqs_bin_bwd) does not depend on the bin count; the knot builder, the bin search and the
+// per-element functions are written once over the bin-count policy Bins<KT> (compile-time K, or
+// K a run-time value up to kAnyMaxK), and so are the coupling-layer kernels further down.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -31,34 +36,83 @@ namespace fs {
 
 constexpr float kMin = 1e-3f;  // DEFAULT_MIN_BIN_WIDTH / HEIGHT / DERIVATIVE (splines.py:6-8)
 
-template <int K>
-struct Knots {
-    float c[K + 1];  // cumulative knots, pinned ends
-    float p[K];      // softmax probabilities
+// ---------------------------------------------------------------------------
+// The bin count of everything below: Bins<KT> is a compile-time K = KT (5, 8, 15, 32), Bins<0> a
+// run-time one, 1 <= K <= kAnyMaxK (fs_rqs_*_any_impl and fs_coupling.any_k: the general-shape
+// mode's training step at a bin count no kernel is instantiated for).  Every spline primitive, row
+// function and kernel is written once over it.  With a compile-time K the loops over the bins
+// unroll whole and the per-thread arrays stay registers; with a run-time K they have kAnyMaxK
+// entries in private memory and the loops run to K.  What else differs lies behind
+// `if constexpr (B::fixed)`: how a bin's knots are read (pick_bin), whether the knot adjoints are
+// kept dense or sparse (rqs_bwd_core, knots_backward), where the adjoints are stored (adj_dst), and
+// both shapes of one statement sequence in knots_pair and density_bwd_row4.  All of this is
+// arranged so that every instantiation compiles to the instruction stream it had when the two
+// families were separate copies ('General-shape mode'): same operations in the same
+// order, so at K in {5, 8, 15, 32} Bins<0> gives what Bins<K> gives up to the compiler's choice of
+// instructions.
+constexpr int kAnyMaxK = 32;
+
+template <int KT>
+struct Bins {
+    static constexpr int kt = KT;
+    static constexpr bool fixed = KT > 0;
+    static constexpr int cap = fixed ? KT : kAnyMaxK;  // of an array over the bins
+    static constexpr int unroll = fixed ? KT + 1 : 4;   // whole loop (at most K + 1 trips) / four scratch loads in flight
+    int rt;  // the run-time K (Bins<0> only)
+    __device__ __forceinline__ int k() const { return fixed ? KT : rt; }
 };
 
-template <int K>
-__device__ __forceinline__ void build_knots(const float *u, float B, Knots<K> &kn) {
+// for (int k = 0; k < n; ++k) { body } in a function templated on the policy B: unrolled whole with a
+// compile-time K (the arrays it indexes stay registers), left to the compiler with a run-time one.
+// A macro, because where a function that took the body is inlined changes the instantiated
+// kernels' instruction streams.
+#define FS_BINS_FOR(k, n, ...)                                              \
+    {                                                                       \
+        if constexpr (B::fixed) {                                           \
+            _Pragma("unroll") for (int k = 0; k < (n); ++k) { __VA_ARGS__ } \
+        } else {                                                            \
+            for (int k = 0; k < (n); ++k) { __VA_ARGS__ }                   \
+        }                                                                   \
+    }
+
+// Where rqs_point_bwd's adjoints go.  With a compile-time K they are collected in registers and
+// stored to their rows afterwards; with a run-time K the arrays are private memory anyway, so those
+// that are stored as they are are written straight to their rows (adj_dst) and only the rescaled
+// ones are left to store.
+template <class B>
+__device__ __forceinline__ float *adj_dst(float *reg, float *row) {
+    return B::fixed ? reg : row;
+}
+
+template <class B>
+struct Knots {
+    float c[B::cap + 1];  // cumulative knots, pinned ends
+    float p[B::cap];      // softmax probabilities
+};
+
+template <class B>
+__device__ __forceinline__ void build_knots(B bins, const float *u, float bound, Knots<B> &kn) {
+    const int K = bins.k();
     float m = u[0];
-#pragma unroll
+#pragma unroll B::unroll
     for (int k = 1; k < K; ++k) m = fmaxf(m, u[k]);
     float s = 0.f;
-#pragma unroll
+#pragma unroll B::unroll
     for (int k = 0; k < K; ++k) {
         kn.p[k] = expf(u[k] - m);
         s += kn.p[k];
     }
-#pragma unroll
+#pragma unroll B::unroll
     for (int k = 0; k < K; ++k) kn.p[k] = kn.p[k] / s;
     const float c1 = 1.f - kMin * (float)K;
     double cs = 0.0;
-    kn.c[0] = -B;
-#pragma unroll
+    kn.c[0] = -bound;
+#pragma unroll B::unroll
     for (int k = 0; k < K - 1; ++k) {
         cs += (double)(kMin + c1 * kn.p[k]);
-        kn.c[k + 1] = (2.f * B) * (float)cs + (-B);
+        kn.c[k + 1] = (2.f * bound) * (float)cs + (-bound);
     }
-    kn.c[K] = B;
+    kn.c[K] = bound;
 }
 
 __device__ __forceinline__ float softplus(float v) { return v > 20.f ? v : log1pf(expf(v)); }
@@ -68,26 +122,32 @@ __device__ __forceinline__ float softplus_grad(float v) {
     return z / (z + 1.f);
 }
 
-// knots c[b], c[b+1] of bin b by a register scan (a dynamically indexed array would live
-// in scratch memory)
-template <int K>
+// knots c[b], c[b+1] of bin b: with a compile-time K by a register scan (a dynamically indexed
+// array would live in scratch memory), with a run-time K the array is there anyway
+template <class B>
 __device__ __forceinline__ void pick_bin(const float *c, int b, float &lo, float &hi) {
-    lo = c[0];
-    hi = c[1];
+    if constexpr (B::fixed) {
+        lo = c[0];
+        hi = c[1];
 #pragma unroll
-    for (int k = 1; k < K; ++k) {
-        if (k == b) {
-            lo = c[k];
-            hi = c[k + 1];
+        for (int k = 1; k < B::kt; ++k) {
+            if (k == b) {
+                lo = c[k];
+                hi = c[k + 1];
+            }
         }
+    } else {
+        lo = c[b];
+        hi = c[b + 1];
     }
 }
 
-// values of the bin that contains x (searchsorted over `knots`, eps on the last one)
-template <int K>
-__device__ __forceinline__ int find_bin(float x, const float *knots) {
+// the bin that contains x (searchsorted over `knots`, eps on the last one)
+template <class B>
+__device__ __forceinline__ int find_bin(B bins, float x, const float *knots) {
+    const int K = bins.k();
     int b = -1;
-#pragma unroll
+#pragma unroll B::unroll
     for (int k = 0; k <= K; ++k) {
         const float kv = (k == K) ? knots[K] + 1e-6f : knots[k];
         b += (x >= kv) ? 1 : 0;
@@ -95,18 +155,16 @@ __device__ __forceinline__ int find_bin(float x, const float *knots) {
     return b < 0 ? 0 : (b > K - 1 ? K - 1 : b);
 }
 
-// one element from its built knots (wc: width knots, hc: height knots); x inside [-B, B]
-template <int K, bool INV>
-__device__ __forceinline__ void rqs_eval_knots(float xv, const float *wc, const float *hc, const float *dd,
-                                               float &out, float &lad, int32_t *nan_flag) {
-    const int b = find_bin<K>(xv, INV ? hc : wc);
-    const float d0 = kMin + softplus(dd[b]), d1 = kMin + softplus(dd[b + 1]);
-    float icw, cw1, ich, ch1;
-    pick_bin<K>(wc, b, icw, cw1);
-    pick_bin<K>(hc, b, ich, ch1);
-    const float ibw = cw1 - icw, ih = ch1 - ich;
-    const float s = ih / ibw;
-    float th;
+// ---------------------------------------------------------------------------
+// One element in its bin: knots (icw, cw1) x (ich, ch1), end derivatives d0, d1.  Nothing here
+// depends on the bin count.
+
+// theta in [0, 1]: forward (x - cw_b) / w_b, inverse the root of the quadratic (a NaN
+// discriminant sets *nan_flag, nullable, right here: reporting it to the caller instead moves the
+// branch and with it the instruction stream of every inverse kernel)
+template <bool INV>
+__device__ __forceinline__ float rqs_bin_theta(float xv, float icw, float ibw, float ich, float ih, float s, float d0,
+                                               float d1, int32_t *nan_flag) {
     if (INV) {
         const float sdd = d0 + d1 - 2.f * s;
         const float a = (xv - ich) * sdd + ih * (s - d0);
@@ -114,10 +172,18 @@ __device__ __forceinline__ void rqs_eval_knots(float xv, const float *wc, const 
         const float c = -s * (xv - ich);
         const float disc = fabsf(bb * bb - 4.f * a * c);
         if (disc != disc && nan_flag) atomicOr(nan_flag, 1);
-        th = (2.f * c) / (-bb - sqrtf(disc));
-    } else {
-        th = (xv - icw) / ibw;
+        return (2.f * c) / (-bb - sqrtf(disc));
     }
+    return (xv - icw) / ibw;
+}
+
+// the rational-quadratic map (forward) or its inverse, and the log|det|
+template <bool INV>
+__device__ __forceinline__ void rqs_bin(float xv, float icw, float cw1, float ich, float ch1, float d0, float d1,
+                                        float &out, float &lad, int32_t *nan_flag) {
+    const float ibw = cw1 - icw, ih = ch1 - ich;
+    const float s = ih / ibw;
+    const float th = rqs_bin_theta<INV>(xv, icw, ibw, ich, ih, s, d0, d1, nan_flag);
     const float t = th * (1.f - th);
     const float den = s + (d0 + d1 - 2.f * s) * t;
     const float A = d1 * th * th + 2.f * s * t + d0 * (1.f - th) * (1.f - th);
@@ -131,74 +197,18 @@ __device__ __forceinline__ void rqs_eval_knots(float xv, const float *wc, const 
     }
 }
 
-// one element: x inside [-B, B] (callers route the outside identity themselves)
-template <int K, bool INV>
-__device__ __forceinline__ void rqs_point(float xv, const float *uw, const float *uh, const float *dd, float B,
-                                          float &out, float &lad, int32_t *nan_flag) {
-    Knots<K> W, Hh;
-    build_knots<K>(uw, B, W);
-    build_knots<K>(uh, B, Hh);
-    rqs_eval_knots<K, INV>(xv, W.c, Hh.c, dd, out, lad, nan_flag);
-}
+// rqs_bin's adjoints from those of out (go) and lad (gl): of x, of the bin's lower knots and its
+// width and height (ibw = cw1 - icw, ih = ch1 - ich), and of d0 and d1
+struct BinGrads {
+    float gx, g_icw, g_ibw, g_ich, g_ih, g_d0, g_d1;
+};
 
-template <int K, bool INV>
-__global__ __launch_bounds__(256) void rqs_forward_kernel(int64_t M, const float *__restrict__ x, const float *__restrict__ uw,
-                                   const float *__restrict__ uh, const float *__restrict__ ud, float B,
-                                   float *__restrict__ out, float *__restrict__ lad, int32_t *__restrict__ nan_flag) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    const float xv = x[i];
-    if (!(xv >= -B && xv <= B)) {
-        out[i] = xv;
-        lad[i] = 0.f;
-        return;
-    }
-    rqs_point<K, INV>(xv, uw + i * K, uh + i * K, ud + i * (K + 1), B, out[i], lad[i], nan_flag);
-}
-
-// knot adjoints (g_c over c[0..K]) -> unnormalised-parameter adjoints
-template <int K>
-__device__ __forceinline__ void knots_backward(const Knots<K> &kn, const float *gc, float B, float *gu) {
-    const float c1 = 1.f - kMin * (float)K;
-    // c[k] = 2B * C[k] - B (k = 1..K-1), C[k] = sum_{j<k} w_j; c[0], c[K] pinned
-    float gw[K];
-    float suffix = 0.f;
-#pragma unroll
-    for (int j = K - 1; j >= 0; --j) {
-        gw[j] = suffix;                                  // sum over k = j+1 .. K-1 of g_C[k]
-        if (j >= 1) suffix += (2.f * B) * gc[j];         // add k = j for the next (smaller) j
-    }
-    float dot = 0.f;
-#pragma unroll
-    for (int j = 0; j < K; ++j) dot += kn.p[j] * (c1 * gw[j]);
-#pragma unroll
-    for (int j = 0; j < K; ++j) gu[j] = kn.p[j] * (c1 * gw[j] - dot);
-}
-
-// the adjoint core of one element inside [-B, B] from its built knots: gx and the
-// adjoints of the bin's knots (gcw / gch over c[0..K]) and derivative logits (gud)
-template <int K, bool INV>
-__device__ __forceinline__ void rqs_bwd_core(float xv, const float *wc, const float *hc, const float *dd, float go,
-                                             float gl, float &gx, float *gcw, float *gch, float *gud) {
-    const int b = find_bin<K>(xv, INV ? hc : wc);
-    const float e0 = dd[b], e1 = dd[b + 1];
-    const float d0 = kMin + softplus(e0), d1 = kMin + softplus(e1);
-    float icw, cw1, ich, ch1;
-    pick_bin<K>(wc, b, icw, cw1);
-    pick_bin<K>(hc, b, ich, ch1);
+template <bool INV>
+__device__ __forceinline__ BinGrads rqs_bin_bwd(float xv, float icw, float cw1, float ich, float ch1, float d0,
+                                                float d1, float go, float gl) {
     const float ibw = cw1 - icw, ih = ch1 - ich;
     const float s = ih / ibw;
-    float th;
-    if (INV) {
-        const float sdd = d0 + d1 - 2.f * s;
-        const float a = (xv - ich) * sdd + ih * (s - d0);
-        const float bb = ih * d0 - (xv - ich) * sdd;
-        const float c = -s * (xv - ich);
-        const float disc = fabsf(bb * bb - 4.f * a * c);
-        th = (2.f * c) / (-bb - sqrtf(disc));
-    } else {
-        th = (xv - icw) / ibw;
-    }
+    const float th = rqs_bin_theta<INV>(xv, icw, ibw, ich, ih, s, d0, d1, nullptr);
     const float t = th * (1.f - th);
     const float omt = 1.f - th;
     const float Nn = s * th * th + d0 * t;
@@ -267,404 +277,167 @@ __device__ __forceinline__ void rqs_bwd_core(float xv, const float *wc, const fl
     // s = h_b / w_b
     g_ih += g_s / ibw;
     g_ibw -= g_s * s / ibw;
-    gx = g_x;
-#pragma unroll
-    for (int k = 0; k <= K; ++k) {
-        gcw[k] = (k == b) ? (g_icw - g_ibw) : ((k == b + 1) ? g_ibw : 0.f);
-        gch[k] = (k == b) ? (g_ich - g_ih) : ((k == b + 1) ? g_ih : 0.f);
-    }
-#pragma unroll
-    for (int k = 0; k <= K; ++k) {
-        float g = 0.f;
-        if (k == b) g = g_d0 * softplus_grad(e0);
-        if (k == b + 1) g = g_d1 * softplus_grad(e1);
-        gud[k] = g;
-    }
-}
-
-// adjoints of one element inside [-B, B]: gx, guw[K], guh[K], gud[K+1]
-template <int K, bool INV>
-__device__ __forceinline__ void rqs_point_bwd(float xv, const float *uw, const float *uh, const float *dd, float B,
-                                              float go, float gl, float &gx, float *guw, float *guh, float *gud) {
-    Knots<K> W, Hh;
-    build_knots<K>(uw, B, W);
-    build_knots<K>(uh, B, Hh);
-    float gcw[K + 1], gch[K + 1];
-    rqs_bwd_core<K, INV>(xv, W.c, Hh.c, dd, go, gl, gx, gcw, gch, gud);
-    knots_backward<K>(W, gcw, B, guw);
-    knots_backward<K>(Hh, gch, B, guh);
-}
-
-template <int K, bool INV>
-__global__ __launch_bounds__(256) void rqs_backward_kernel(int64_t M, const float *__restrict__ x, const float *__restrict__ uw,
-                                    const float *__restrict__ uh, const float *__restrict__ ud, float B,
-                                    const float *__restrict__ g_out, const float *__restrict__ g_lad,
-                                    float *__restrict__ gx, float *__restrict__ guw, float *__restrict__ guh,
-                                    float *__restrict__ gud) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    const float xv = x[i];
-    const float go = g_out ? g_out[i] : 0.f, gl = g_lad ? g_lad[i] : 0.f;
-    if (!(xv >= -B && xv <= B)) {
-        gx[i] = go;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            guw[i * K + k] = 0.f;
-            guh[i * K + k] = 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k <= K; ++k) gud[i * (K + 1) + k] = 0.f;
-        return;
-    }
-    float a[K], b[K], d[K + 1];
-    rqs_point_bwd<K, INV>(xv, uw + i * K, uh + i * K, ud + i * (K + 1), B, go, gl, gx[i], a, b, d);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        guw[i * K + k] = a[k];
-        guh[i * K + k] = b[k];
-    }
-#pragma unroll
-    for (int k = 0; k <= K; ++k) gud[i * (K + 1) + k] = d[k];
+    return BinGrads{g_x, g_icw, g_ibw, g_ich, g_ih, g_d0, g_d1};
 }
 
 // ---------------------------------------------------------------------------
-// The same two kernels with K a run-time value, 1 <= K <= kAnyMaxK (fs_rqs_forward_any /
-// fs_rqs_backward_any): the operations of build_knots, find_bin, rqs_eval_knots,
-// rqs_bwd_core and knots_backward in the same order, on arrays of kAnyMaxK with K as the
-// loop bound (they live in private memory, so a bin is a plain index).
-constexpr int kAnyMaxK = 32;
-
-struct KnotsAny {
-    float c[kAnyMaxK + 1];
-    float p[kAnyMaxK];
-};
-
-__device__ __forceinline__ void build_knots_any(int K, const float *u, float B, KnotsAny &kn) {
-    float m = u[0];
-#pragma unroll 4
-    for (int k = 1; k < K; ++k) m = fmaxf(m, u[k]);
-    float s = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-        kn.p[k] = expf(u[k] - m);
-        s += kn.p[k];
-    }
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) kn.p[k] = kn.p[k] / s;
-    const float c1 = 1.f - kMin * (float)K;
-    double cs = 0.0;
-    kn.c[0] = -B;
-#pragma unroll 4
-    for (int k = 0; k < K - 1; ++k) {
-        cs += (double)(kMin + c1 * kn.p[k]);
-        kn.c[k + 1] = (2.f * B) * (float)cs + (-B);
-    }
-    kn.c[K] = B;
-}
-
-__device__ __forceinline__ int find_bin_any(int K, float x, const float *knots) {
-    int b = -1;
-#pragma unroll 4
-    for (int k = 0; k <= K; ++k) {
-        const float kv = (k == K) ? knots[K] + 1e-6f : knots[k];
-        b += (x >= kv) ? 1 : 0;
-    }
-    return b < 0 ? 0 : (b > K - 1 ? K - 1 : b);
-}
-
-// rqs_eval_knots: one element from its built knots; x inside [-B, B]
-template <bool INV>
-__device__ __forceinline__ void rqs_eval_knots_any(int K, float xv, const float *wc, const float *hc,
-                                                   const float *dd, float &out, float &lad, int32_t *nan_flag) {
-    const int b = find_bin_any(K, xv, INV ? hc : wc);
+// one element from its built knots (wc: width knots, hc: height knots); x inside [-B, B]
+template <bool INV, class B>
+__device__ __forceinline__ void rqs_eval_knots(B bins, float xv, const float *wc, const float *hc, const float *dd,
+                                               float &out, float &lad, int32_t *nan_flag) {
+    const int b = find_bin(bins, xv, INV ? hc : wc);
     const float d0 = kMin + softplus(dd[b]), d1 = kMin + softplus(dd[b + 1]);
-    const float icw = wc[b], cw1 = wc[b + 1], ich = hc[b], ch1 = hc[b + 1];
-    const float ibw = cw1 - icw, ih = ch1 - ich;
-    const float s = ih / ibw;
-    float th;
-    if (INV) {
-        const float sdd = d0 + d1 - 2.f * s;
-        const float a = (xv - ich) * sdd + ih * (s - d0);
-        const float bb = ih * d0 - (xv - ich) * sdd;
-        const float c = -s * (xv - ich);
-        const float disc = fabsf(bb * bb - 4.f * a * c);
-        if (disc != disc && nan_flag) atomicOr(nan_flag, 1);
-        th = (2.f * c) / (-bb - sqrtf(disc));
-    } else {
-        th = (xv - icw) / ibw;
-    }
-    const float t = th * (1.f - th);
-    const float den = s + (d0 + d1 - 2.f * s) * t;
-    const float A = d1 * th * th + 2.f * s * t + d0 * (1.f - th) * (1.f - th);
-    const float l = logf(s * s * A) - 2.f * logf(den);
-    if (INV) {
-        out = th * ibw + icw;
-        lad = -l;
-    } else {
-        out = ich + ih * (s * th * th + d0 * t) / den;
-        lad = l;
-    }
+    float icw, cw1, ich, ch1;
+    pick_bin<B>(wc, b, icw, cw1);
+    pick_bin<B>(hc, b, ich, ch1);
+    rqs_bin<INV>(xv, icw, cw1, ich, ch1, d0, d1, out, lad, nan_flag);
 }
 
-template <bool INV>
-__device__ __forceinline__ void rqs_point_any(int K, float xv, const float *uw, const float *uh, const float *dd,
-                                              float B, float &out, float &lad, int32_t *nan_flag) {
-    KnotsAny W, Hh;
-    build_knots_any(K, uw, B, W);
-    build_knots_any(K, uh, B, Hh);
-    rqs_eval_knots_any<INV>(K, xv, W.c, Hh.c, dd, out, lad, nan_flag);
+// one element: x inside [-B, B] (callers route the outside identity themselves)
+template <bool INV, class B>
+__device__ __forceinline__ void rqs_point(B bins, float xv, const float *uw, const float *uh, const float *dd,
+                                          float bound, float &out, float &lad, int32_t *nan_flag) {
+    Knots<B> W, Hh;
+    build_knots(bins, uw, bound, W);
+    build_knots(bins, uh, bound, Hh);
+    rqs_eval_knots<INV>(bins, xv, W.c, Hh.c, dd, out, lad, nan_flag);
 }
 
-template <bool INV>
-__global__ __launch_bounds__(256) void rqs_forward_any_kernel(int64_t M, int K, const float *__restrict__ x,
-                                                              const float *__restrict__ uw,
-                                                              const float *__restrict__ uh,
-                                                              const float *__restrict__ ud, float B,
-                                                              float *__restrict__ out, float *__restrict__ lad,
-                                                              int32_t *__restrict__ nan_flag) {
+// KT: Bins<KT>, with Krt the run-time bin count of Bins<0> (last, so that the instantiated
+// kernels' other arguments keep their offsets)
+template <int KT, bool INV>
+__global__ __launch_bounds__(256) void rqs_forward_kernel(int64_t M, const float *__restrict__ x, const float *__restrict__ uw,
+                                   const float *__restrict__ uh, const float *__restrict__ ud, float bound,
+                                   float *__restrict__ out, float *__restrict__ lad, int32_t *__restrict__ nan_flag,
+                                   int Krt) {
+    const Bins<KT> bins{Krt};
+    const int K = bins.k();
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
     const float xv = x[i];
-    if (!(xv >= -B && xv <= B)) {
+    if (!(xv >= -bound && xv <= bound)) {
         out[i] = xv;
         lad[i] = 0.f;
         return;
     }
-    rqs_point_any<INV>(K, xv, uw + i * K, uh + i * K, ud + i * (K + 1), B, out[i], lad[i], nan_flag);
+    rqs_point<INV>(bins, xv, uw + i * K, uh + i * K, ud + i * (K + 1), bound, out[i], lad[i], nan_flag);
 }
 
-// knot adjoints (g_b at knot b, g_b1 at knot b + 1, zero elsewhere) -> unnormalised-parameter
-// adjoints: knots_backward on that sparse gc
-__device__ __forceinline__ void knots_backward_any(int K, const KnotsAny &kn, int b, float g_b, float g_b1, float B,
-                                                   float *gu) {
-    const float c1 = 1.f - kMin * (float)K;
-    float gw[kAnyMaxK];
-    float suffix = 0.f;
-#pragma unroll 4
-    for (int j = K - 1; j >= 0; --j) {
-        gw[j] = suffix;
-        const float gcj = (j == b) ? g_b : ((j == b + 1) ? g_b1 : 0.f);
-        if (j >= 1) suffix += (2.f * B) * gcj;
-    }
-    float dot = 0.f;
-#pragma unroll 4
-    for (int j = 0; j < K; ++j) dot += kn.p[j] * (c1 * gw[j]);
-#pragma unroll 4
-    for (int j = 0; j < K; ++j) gu[j] = kn.p[j] * (c1 * gw[j] - dot);
-}
-
-// rqs_bwd_core with the knot adjoints left sparse: only knots b and b + 1 of the element's
-// bin carry one (gw0 / gw1 of the width knots, gh0 / gh1 of the height knots)
+// The knot adjoints of one element: only knots b and b + 1 of its bin carry one (gw0 / gw1 of the
+// width knots, gh0 / gh1 of the height knots).  With a compile-time K they are also spread over
+// dense register arrays g_c[0..K], which the instantiated kernels read; with a run-time K they stay
+// sparse.
 struct BinAdjoint {
     int b;
     float gw0, gw1, gh0, gh1;
 };
 
-// the adjoint core of one element inside [-B, B] from its built knots: gx, the bin's knot
-// adjoints and the derivative logits' adjoints gud[0..K]
-template <bool INV>
-__device__ __forceinline__ BinAdjoint rqs_bwd_core_any(int K, float xv, const float *wc, const float *hc,
-                                                       const float *dd, float go, float gl, float &gx, float *gud) {
-    const int b = find_bin_any(K, xv, INV ? hc : wc);
+// knot adjoints -> unnormalised-parameter adjoints; the knot adjoints are gc over c[0..K] with a
+// compile-time K, else g_b at knot b, g_b1 at knot b + 1 and zero elsewhere
+template <class B>
+__device__ __forceinline__ void knots_backward(B bins, const Knots<B> &kn, const float *gc, int b, float g_b,
+                                               float g_b1, float bound, float *gu) {
+    const int K = bins.k();
+    const float c1 = 1.f - kMin * (float)K;
+    // c[k] = 2B * C[k] - B (k = 1..K-1), C[k] = sum_{j<k} w_j; c[0], c[K] pinned
+    float gw[B::cap];
+    float suffix = 0.f;
+#pragma unroll B::unroll
+    for (int j = K - 1; j >= 0; --j) {
+        gw[j] = suffix;  // sum over k = j+1 .. K-1 of g_C[k]
+        float gcj;
+        if constexpr (B::fixed)
+            gcj = gc[j];
+        else
+            gcj = (j == b) ? g_b : ((j == b + 1) ? g_b1 : 0.f);
+        if (j >= 1) suffix += (2.f * bound) * gcj;  // add k = j for the next (smaller) j
+    }
+    float dot = 0.f;
+#pragma unroll B::unroll
+    for (int j = 0; j < K; ++j) dot += kn.p[j] * (c1 * gw[j]);
+#pragma unroll B::unroll
+    for (int j = 0; j < K; ++j) gu[j] = kn.p[j] * (c1 * gw[j] - dot);
+}
+
+// the adjoint core of one element inside [-B, B] from its built knots: gx, the bin's knot adjoints
+// (with a compile-time K also as gcw / gch over c[0..K]) and the derivative logits' adjoints
+// gud[0..K]
+template <bool INV, class B>
+__device__ __forceinline__ BinAdjoint rqs_bwd_core(B bins, float xv, const float *wc, const float *hc,
+                                                   const float *dd, float go, float gl, float &gx, float *gcw,
+                                                   float *gch, float *gud) {
+    const int K = bins.k();
+    const int b = find_bin(bins, xv, INV ? hc : wc);
     const float e0 = dd[b], e1 = dd[b + 1];
     const float d0 = kMin + softplus(e0), d1 = kMin + softplus(e1);
-    const float icw = wc[b], cw1 = wc[b + 1], ich = hc[b], ch1 = hc[b + 1];
-    const float ibw = cw1 - icw, ih = ch1 - ich;
-    const float s = ih / ibw;
-    float th;
-    if (INV) {
-        const float sdd = d0 + d1 - 2.f * s;
-        const float a = (xv - ich) * sdd + ih * (s - d0);
-        const float bb = ih * d0 - (xv - ich) * sdd;
-        const float c = -s * (xv - ich);
-        const float disc = fabsf(bb * bb - 4.f * a * c);
-        th = (2.f * c) / (-bb - sqrtf(disc));
-    } else {
-        th = (xv - icw) / ibw;
+    float icw, cw1, ich, ch1;
+    pick_bin<B>(wc, b, icw, cw1);
+    pick_bin<B>(hc, b, ich, ch1);
+    const BinGrads r = rqs_bin_bwd<INV>(xv, icw, cw1, ich, ch1, d0, d1, go, gl);
+    gx = r.gx;
+    if constexpr (B::fixed) {
+#pragma unroll
+        for (int k = 0; k <= K; ++k) {
+            gcw[k] = (k == b) ? (r.g_icw - r.g_ibw) : ((k == b + 1) ? r.g_ibw : 0.f);
+            gch[k] = (k == b) ? (r.g_ich - r.g_ih) : ((k == b + 1) ? r.g_ih : 0.f);
+        }
     }
-    const float t = th * (1.f - th);
-    const float omt = 1.f - th;
-    const float Nn = s * th * th + d0 * t;
-    const float den = s + (d0 + d1 - 2.f * s) * t;
-    const float A = d1 * th * th + 2.f * s * t + d0 * omt * omt;
-    const float dnum = s * s * A;
-    float g_th = 0.f, g_s = 0.f, g_t = 0.f, g_d0 = 0.f, g_d1 = 0.f;
-    float g_icw = 0.f, g_ibw = 0.f, g_ich = 0.f, g_ih = 0.f, g_x = 0.f;
-    const float gll = INV ? -gl : gl;
-    {
-        const float g_dnum = gll / dnum;
-        const float g_den = -2.f * gll / den;
-        const float g_A = g_dnum * s * s;
-        g_s += g_dnum * 2.f * s * A + g_A * 2.f * t;
-        g_d1 += g_A * th * th;
-        g_d0 += g_A * omt * omt;
-        g_th += g_A * (2.f * d1 * th - 2.f * d0 * omt);
-        g_t += g_A * 2.f * s;
-        g_s += g_den * (1.f - 2.f * t);
-        g_d0 += g_den * t;
-        g_d1 += g_den * t;
-        g_t += g_den * (d0 + d1 - 2.f * s);
-    }
-    if (INV) {
-        g_th += go * ibw;
-        g_icw += go;
-        g_ibw += go * th;
-        g_th += g_t * (1.f - 2.f * th);
-        const float N_th = 2.f * s * th + d0 * (1.f - 2.f * th);
-        const float den_th = (d0 + d1 - 2.f * s) * (1.f - 2.f * th);
-        const float F_th = ih * (N_th * den - Nn * den_th) / (den * den);
-        const float F_s = ih * (th * th * den - Nn * (1.f - 2.f * t)) / (den * den);
-        const float F_d0 = ih * (t * den - Nn * t) / (den * den);
-        const float F_d1 = -ih * Nn * t / (den * den);
-        const float wgt = g_th / F_th;
-        g_x += wgt;
-        g_ich -= wgt;
-        g_ih -= wgt * Nn / den;
-        g_s -= wgt * F_s;
-        g_d0 -= wgt * F_d0;
-        g_d1 -= wgt * F_d1;
-    } else {
-        const float g_num = go / den;
-        const float g_den = -go * (ih * Nn) / (den * den);
-        g_ich += go;
-        g_ih += g_num * Nn;
-        const float g_N = g_num * ih;
-        g_s += g_N * th * th;
-        g_th += g_N * 2.f * s * th;
-        g_d0 += g_N * t;
-        g_t += g_N * d0;
-        g_s += g_den * (1.f - 2.f * t);
-        g_d0 += g_den * t;
-        g_d1 += g_den * t;
-        g_t += g_den * (d0 + d1 - 2.f * s);
-        g_th += g_t * (1.f - 2.f * th);
-        g_x += g_th / ibw;
-        g_icw -= g_th / ibw;
-        g_ibw -= g_th * th / ibw;
-    }
-    g_ih += g_s / ibw;
-    g_ibw -= g_s * s / ibw;
-    gx = g_x;
-    for (int k = 0; k <= K; ++k) {
-        float g = 0.f;
-        if (k == b) g = g_d0 * softplus_grad(e0);
-        if (k == b + 1) g = g_d1 * softplus_grad(e1);
-        gud[k] = g;
-    }
-    return BinAdjoint{b, g_icw - g_ibw, g_ibw, g_ich - g_ih, g_ih};
+    FS_BINS_FOR(k, K + 1,
+                float g = 0.f;
+                if (k == b) g = r.g_d0 * softplus_grad(e0);
+                if (k == b + 1) g = r.g_d1 * softplus_grad(e1);
+                gud[k] = g;)
+    return BinAdjoint{b, r.g_icw - r.g_ibw, r.g_ibw, r.g_ich - r.g_ih, r.g_ih};
 }
 
 // adjoints of one element inside [-B, B]: gx, guw[K], guh[K], gud[K+1]
-template <bool INV>
-__device__ __forceinline__ void rqs_point_bwd_any(int K, float xv, const float *uw, const float *uh, const float *dd,
-                                                  float B, float go, float gl, float &gx, float *guw, float *guh,
-                                                  float *gud) {
-    KnotsAny W, Hh;
-    build_knots_any(K, uw, B, W);
-    build_knots_any(K, uh, B, Hh);
-    const BinAdjoint a = rqs_bwd_core_any<INV>(K, xv, W.c, Hh.c, dd, go, gl, gx, gud);
-    knots_backward_any(K, W, a.b, a.gw0, a.gw1, B, guw);
-    knots_backward_any(K, Hh, a.b, a.gh0, a.gh1, B, guh);
+template <bool INV, class B>
+__device__ __forceinline__ void rqs_point_bwd(B bins, float xv, const float *uw, const float *uh, const float *dd,
+                                              float bound, float go, float gl, float &gx, float *guw, float *guh,
+                                              float *gud) {
+    Knots<B> W, Hh;
+    build_knots(bins, uw, bound, W);
+    build_knots(bins, uh, bound, Hh);
+    float gcw[B::cap + 1], gch[B::cap + 1];
+    const BinAdjoint a = rqs_bwd_core<INV>(bins, xv, W.c, Hh.c, dd, go, gl, gx, gcw, gch, gud);
+    knots_backward(bins, W, gcw, a.b, a.gw0, a.gw1, bound, guw);
+    knots_backward(bins, Hh, gch, a.b, a.gh0, a.gh1, bound, guh);
 }
 
-template <bool INV>
-__global__ __launch_bounds__(256) void rqs_backward_any_kernel(int64_t M, int K, const float *__restrict__ x,
-                                                               const float *__restrict__ uw,
-                                                               const float *__restrict__ uh,
-                                                               const float *__restrict__ ud, float B,
-                                                               const float *__restrict__ g_out,
-                                                               const float *__restrict__ g_lad,
-                                                               float *__restrict__ gx, float *__restrict__ guw,
-                                                               float *__restrict__ guh, float *__restrict__ gud) {
+template <int KT, bool INV>
+__global__ __launch_bounds__(256) void rqs_backward_kernel(int64_t M, const float *__restrict__ x, const float *__restrict__ uw,
+                                    const float *__restrict__ uh, const float *__restrict__ ud, float bound,
+                                    const float *__restrict__ g_out, const float *__restrict__ g_lad,
+                                    float *__restrict__ gx, float *__restrict__ guw, float *__restrict__ guh,
+                                    float *__restrict__ gud, int Krt) {
+    using B = Bins<KT>;
+    const B bins{Krt};
+    const int K = bins.k();
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
     const float xv = x[i];
     const float go = g_out ? g_out[i] : 0.f, gl = g_lad ? g_lad[i] : 0.f;
-    float *pw = guw + i * K, *ph = guh + i * K, *pd = gud + i * (K + 1);
-    if (!(xv >= -B && xv <= B)) {
+    // with a run-time K the adjoints go straight to their rows (adj_dst); the pointers are formed
+    // here, before the branch, and only then: either way moved changes the other policy's kernels
+    float *pw = nullptr, *ph = nullptr, *pd = nullptr;
+    if constexpr (!B::fixed) {
+        pw = guw + i * K;
+        ph = guh + i * K;
+        pd = gud + i * (K + 1);
+    }
+    if (!(xv >= -bound && xv <= bound)) {
         gx[i] = go;
-        for (int k = 0; k < K; ++k) {
-            pw[k] = 0.f;
-            ph[k] = 0.f;
-        }
-        for (int k = 0; k <= K; ++k) pd[k] = 0.f;
+        FS_BINS_FOR(k, K, guw[i * K + k] = 0.f; guh[i * K + k] = 0.f;)
+        FS_BINS_FOR(k, K + 1, gud[i * (K + 1) + k] = 0.f;)
         return;
     }
-    rqs_point_bwd_any<INV>(K, xv, uw + i * K, uh + i * K, ud + i * (K + 1), B, go, gl, gx[i], pw, ph, pd);
-}
-
-// ---------------------------------------------------------------------------
-// The bin count of the coupling kernels below: Bins<KT> is a compile-time K = KT (5, 8, 15, 32),
-// Bins<0> a run-time one, 1 <= K <= kAnyMaxK (fs_coupling.any_k: the general-shape mode's training
-// step at a bin count no kernel is instantiated for).  Each row function and kernel is written once
-// over it.  What differs between the two lies behind the policy: the spline family underneath (the
-// instantiated one scans registers; the _any one indexes per-thread arrays of kAnyMaxK in private
-// memory and keeps the knot adjoints sparse), the arrays' capacity, the loops' unrolling and where
-// the adjoints are stored (adj_dst).  knots_pair and density_bwd_row4 keep both shapes of one
-// statement sequence behind `if constexpr (B::fixed)`.  All of this is arranged so that every
-// instantiation compiles to the instruction stream it had as a separate copy (DESIGN.md,
-// 'General-shape mode'): same operations in the same order, so each row is what the single-layer
-// entry points give, and at K in {5, 8, 15, 32} Bins<0> gives what Bins<K> gives up to the
-// compiler's choice of instructions.
-template <int KT>
-struct Bins {
-    static constexpr int kt = KT;
-    static constexpr bool fixed = KT > 0;
-    static constexpr int cap = fixed ? KT : kAnyMaxK;  // of an array over the bins
-    static constexpr int unroll = fixed ? KT + 1 : 4;   // whole loop (at most K + 1 trips) / as the _any family
-    using KnotSet = std::conditional_t<fixed, Knots<KT>, KnotsAny>;
-    int rt;  // the run-time K (Bins<0> only)
-    __device__ __forceinline__ int k() const { return fixed ? KT : rt; }
-};
-
-// for (int k = 0; k < n; ++k) { body } in a function templated on the policy B: unrolled whole with a
-// compile-time K (the arrays it indexes stay registers), left to the compiler with a run-time one.
-// A macro, because where a function that took the body is inlined changes the instantiated
-// kernels' instruction streams.
-#define FS_BINS_FOR(k, n, ...)                                              \
-    {                                                                       \
-        if constexpr (B::fixed) {                                           \
-            _Pragma("unroll") for (int k = 0; k < (n); ++k) { __VA_ARGS__ } \
-        } else {                                                            \
-            for (int k = 0; k < (n); ++k) { __VA_ARGS__ }                   \
-        }                                                                   \
+    float a[B::cap], b[B::cap], d[B::cap + 1];
+    rqs_point_bwd<INV>(bins, xv, uw + i * K, uh + i * K, ud + i * (K + 1), bound, go, gl, gx[i], adj_dst<B>(a, pw),
+                       adj_dst<B>(b, ph), adj_dst<B>(d, pd));
+    if constexpr (B::fixed) {
+        FS_BINS_FOR(k, K, guw[i * K + k] = a[k]; guh[i * K + k] = b[k];)
+        FS_BINS_FOR(k, K + 1, gud[i * (K + 1) + k] = d[k];)
     }
-
-// the spline primitives of either family
-template <class B>
-__device__ __forceinline__ void bins_build_knots(B bins, const float *u, float bound, typename B::KnotSet &kn) {
-    if constexpr (B::fixed)
-        build_knots<B::kt>(u, bound, kn);
-    else
-        build_knots_any(bins.rt, u, bound, kn);
-}
-
-template <bool INV, class B>
-__device__ __forceinline__ void bins_eval_knots(B bins, float xv, const float *wc, const float *hc, const float *dd,
-                                                float &out, float &lad, int32_t *nan_flag) {
-    if constexpr (B::fixed)
-        rqs_eval_knots<B::kt, INV>(xv, wc, hc, dd, out, lad, nan_flag);
-    else
-        rqs_eval_knots_any<INV>(bins.rt, xv, wc, hc, dd, out, lad, nan_flag);
-}
-
-template <bool INV, class B>
-__device__ __forceinline__ void bins_point(B bins, float xv, const float *uw, const float *uh, const float *dd,
-                                           float bound, float &out, float &lad, int32_t *nan_flag) {
-    if constexpr (B::fixed)
-        rqs_point<B::kt, INV>(xv, uw, uh, dd, bound, out, lad, nan_flag);
-    else
-        rqs_point_any<INV>(bins.rt, xv, uw, uh, dd, bound, out, lad, nan_flag);
-}
-
-template <bool INV, class B>
-__device__ __forceinline__ void bins_point_bwd(B bins, float xv, const float *uw, const float *uh, const float *dd,
-                                               float bound, float go, float gl, float &gx, float *guw, float *guh,
-                                               float *gud) {
-    if constexpr (B::fixed)
-        rqs_point_bwd<B::kt, INV>(xv, uw, uh, dd, bound, go, gl, gx, guw, guh, gud);
-    else
-        rqs_point_bwd_any<INV>(bins.rt, xv, uw, uh, dd, bound, go, gl, gx, guw, guh, gud);
 }
 
 // ---------------------------------------------------------------------------
@@ -724,11 +497,11 @@ __device__ __forceinline__ void density_fwd_row(B bins, const CouplingArgs &c, c
             const float *p = d.params + (row * c.n + j) * (3 * K + 1);
             float w[B::cap], h[B::cap];
             cond_params(bins, p, c.sq, w, h);
-            bins_point<false>(bins, xt, w, h, p + 2 * K, c.bound, yt, lt, nullptr);
+            rqs_point<false>(bins, xt, w, h, p + 2 * K, c.bound, yt, lt, nullptr);
         }
         float yi = xi, li = 0.f;
         if (xi >= -c.bound && xi <= c.bound)
-            bins_point<false>(bins, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
+            rqs_point<false>(bins, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
         d.out[row * c.D + (pt + c.D - c.split) % c.D] = yt;
         d.out[row * c.D + (pi + c.D - c.split) % c.D] = yi;
         if (rb) {  // the row for the next layer's features in the same launch
@@ -748,15 +521,6 @@ template <int KT>
 __global__ __launch_bounds__(256) void coupling_density_fwd_kernel(CouplingArgs c, DensityFwdArgs d) {
     const int64_t row = (int64_t)blockIdx.x * kCplRows + (threadIdx.x >> 6);
     if (row < c.rows) density_fwd_row(Bins<KT>{c.K}, c, d, row);
-}
-
-// Where bins_point_bwd's adjoints go.  With a compile-time K they are collected in registers and
-// stored to their rows afterwards; with a run-time K the arrays are private memory anyway, so those
-// that are stored as they are are written straight to their rows (adj_dst) and only the rescaled
-// ones are left to store.
-template <class B>
-__device__ __forceinline__ float *adj_dst(float *reg, float *row) {
-    return B::fixed ? reg : row;
 }
 
 // density_fwd_row's adjoints: gx (both halves, spline part), g_params [rows][n][3K+1], g_u the
@@ -791,7 +555,7 @@ __device__ __forceinline__ void density_bwd_row(B bins, const CouplingArgs &c, c
             float w[B::cap], h[B::cap];
             cond_params(bins, p, c.sq, w, h);
             float g;
-            bins_point_bwd<false>(bins, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, adj_dst<B>(gd, gp + 2 * K));
+            rqs_point_bwd<false>(bins, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, adj_dst<B>(gd, gp + 2 * K));
             gx[row * c.D + pt] = g;
             FS_BINS_FOR(k, K, gp[k] = gw[k] / c.sq; gp[K + k] = gh[k] / c.sq;)
             if constexpr (B::fixed) FS_BINS_FOR(k, K + 1, gp[2 * K + k] = gd[k];)
@@ -802,7 +566,7 @@ __device__ __forceinline__ void density_bwd_row(B bins, const CouplingArgs &c, c
         if (part == 0) {
         } else if (xi >= -c.bound && xi <= c.bound) {
             float g;
-            bins_point_bwd<false>(bins, xi, uw + j * K, uh + j * K, ud + j * (K + 1), c.bound, goi, gl, g,
+            rqs_point_bwd<false>(bins, xi, uw + j * K, uh + j * K, ud + j * (K + 1), c.bound, goi, gl, g,
                                   adj_dst<B>(gw, guw), adj_dst<B>(gh, guh), adj_dst<B>(gd, gud));
             gx[row * c.D + pi] = g;
             if constexpr (B::fixed) {
@@ -924,7 +688,7 @@ __device__ __forceinline__ void sample_pre_row(B bins, const CouplingArgs &c, co
         const float xi = zr[(pi + c.split) % c.D];
         float yi = xi, li = 0.f;
         if (xi >= -c.bound && xi <= c.bound)
-            bins_point<true>(bins, xi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, yi, li, s.nan_flag);
+            rqs_point<true>(bins, xi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, yi, li, s.nan_flag);
         const float v = c.scale * yi;
         s.t[row * 2 * c.n + j] = cosf(v);
         s.t[row * 2 * c.n + c.n + j] = sinf(v);
@@ -967,7 +731,7 @@ __device__ __forceinline__ void sample_post_row(B bins, const CouplingArgs &c, c
             const float *p = s.params + (row * c.n + j) * (3 * K + 1);
             float w[B::cap], h[B::cap];
             cond_params(bins, p, c.sq, w, h);
-            bins_point<true>(bins, xt, w, h, p + 2 * K, c.bound, yt, lt, s.nan_flag);
+            rqs_point<true>(bins, xt, w, h, p + 2 * K, c.bound, yt, lt, s.nan_flag);
         }
         s.out[row * c.D + pt] = yt;
         if (rb) rb[pt] = yt;
@@ -1099,17 +863,17 @@ __device__ __forceinline__ void sample_post_row2(B bins, const CouplingArgs &c, 
         }
         const float xt = s.out[row * c.D + pt];
         const float *p = s.params + (row * c.n + jj) * (3 * K + 1);
-        typename B::KnotSet kn;
+        Knots<B> kn;
         {
             float u[B::cap];
             FS_BINS_FOR(k, K, u[k] = p[h * K + k] / c.sq;)  // cond_params' half
-            bins_build_knots(bins, u, c.bound, kn);
+            build_knots(bins, u, c.bound, kn);
         }
         float wc[B::cap + 1], hc[B::cap + 1];
         knots_pair(bins, kx, h, h, kn.c, wc, hc);
         float yt = xt, lt = 0.f;
         if (on && xt >= -c.bound && xt <= c.bound)
-            bins_eval_knots<true>(bins, xt, wc, hc, p + 2 * K, yt, lt, h == 0 ? s.nan_flag : nullptr);
+            rqs_eval_knots<true>(bins, xt, wc, hc, p + 2 * K, yt, lt, h == 0 ? s.nan_flag : nullptr);
         if (h == 0 && on) {
             s.out[row * c.D + pt] = yt;
             rb[pt] = yt;
@@ -1134,13 +898,13 @@ __device__ __forceinline__ void sample_pre_row2(B bins, const CouplingArgs &c, c
         const int jj = on ? j : 0;
         const int pi = (int)c.id[jj], pt = (int)c.tr[jj];
         const float xi = zr[(pi + c.split) % c.D];
-        typename B::KnotSet kn;
-        bins_build_knots(bins, (h == 0 ? s.uw : s.uh) + jj * K, c.bound, kn);
+        Knots<B> kn;
+        build_knots(bins, (h == 0 ? s.uw : s.uh) + jj * K, c.bound, kn);
         float wc[B::cap + 1], hc[B::cap + 1];
         knots_pair(bins, kx, h, h, kn.c, wc, hc);
         float yi = xi, li = 0.f;
         if (on && xi >= -c.bound && xi <= c.bound)
-            bins_eval_knots<true>(bins, xi, wc, hc, s.ud + jj * (K + 1), yi, li, h == 0 ? s.nan_flag : nullptr);
+            rqs_eval_knots<true>(bins, xi, wc, hc, s.ud + jj * (K + 1), yi, li, h == 0 ? s.nan_flag : nullptr);
         const float v = c.scale * yi;
         if (on) {
             if (h == 0) {
@@ -1175,7 +939,7 @@ __device__ __forceinline__ float density_fwd_row2(B bins, const CouplingArgs &c,
                 const float *p = d.params + (row * c.n + j) * (3 * K + 1);
                 float w[B::cap], hh[B::cap];
                 cond_params(bins, p, c.sq, w, hh);
-                bins_point<false>(bins, xt, w, hh, p + 2 * K, c.bound, yt, lt, nullptr);
+                rqs_point<false>(bins, xt, w, hh, p + 2 * K, c.bound, yt, lt, nullptr);
             }
             d.out[row * c.D + (pt + c.D - c.split) % c.D] = yt;
             rb[(pt + c.D - c.split) % c.D] = yt;
@@ -1185,7 +949,7 @@ __device__ __forceinline__ float density_fwd_row2(B bins, const CouplingArgs &c,
             const float xi = xr[pi];
             float yi = xi, li = 0.f;
             if (xi >= -c.bound && xi <= c.bound)
-                bins_point<false>(bins, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
+                rqs_point<false>(bins, xi, d.uw + j * K, d.uh + j * K, d.ud + j * (K + 1), c.bound, yi, li, nullptr);
             d.out[row * c.D + (pi + c.D - c.split) % c.D] = yi;
             rb[(pi + c.D - c.split) % c.D] = yi;
             sl += li;
@@ -1251,13 +1015,13 @@ __device__ __forceinline__ void density_bwd_row4(B bins, const CouplingArgs &c, 
         const float xv = xr[pos];
         const float go = gor ? gor[(pos + c.D - c.split) % c.D] : 0.f;
         const float *p = params + (row * c.n + jj) * P;
-        typename B::KnotSet kn;
+        Knots<B> kn;
         if (part == 0) {
             float u[B::cap];
             FS_BINS_FOR(k, K, u[k] = p[h * K + k] / c.sq;)  // cond_params' half
-            bins_build_knots(bins, u, c.bound, kn);
+            build_knots(bins, u, c.bound, kn);
         } else {
-            bins_build_knots(bins, (h == 0 ? uw : uh) + jj * K, c.bound, kn);
+            build_knots(bins, (h == 0 ? uw : uh) + jj * K, c.bound, kn);
         }
         float wc[B::cap + 1], hc[B::cap + 1];
         knots_pair(bins, kx, wv, h, kn.c, wc, hc);
@@ -1268,17 +1032,17 @@ __device__ __forceinline__ void density_bwd_row4(B bins, const CouplingArgs &c, 
         float *guh = guw + c.n * K;
         float *gud = g_u + row * c.n * P + 2 * c.n * K + jj * (K + 1);
         // each wave stores its knot set's parameter adjoints and, on h == 0, gx and the derivative
-        // logits' adjoints.  The two spline families hand back the knot adjoints differently
-        // (dense / sparse), and the stores keep the shape each had
+        // logits' adjoints.  The two policies read the knot adjoints differently (dense / sparse),
+        // and the stores keep the shape each had as a separate copy
         if constexpr (B::fixed) {
             if (on && inside) {
                 float g, gcw[B::cap + 1], gch[B::cap + 1], gd[B::cap + 1];
-                rqs_bwd_core<B::kt, false>(xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1), go, gl, g, gcw, gch,
-                                           gd);
+                const BinAdjoint a = rqs_bwd_core<false>(bins, xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1),
+                                                         go, gl, g, gcw, gch, gd);
                 float gsel[B::cap + 1], gk[B::cap];
 #pragma unroll
                 for (int k = 0; k <= K; ++k) gsel[k] = h == 0 ? gcw[k] : gch[k];
-                knots_backward<B::kt>(kn, gsel, c.bound, gk);
+                knots_backward(bins, kn, gsel, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
                 if (part == 0) {
 #pragma unroll
                     for (int k = 0; k < K; ++k) gp[h * K + k] = gk[k] / c.sq;
@@ -1322,9 +1086,9 @@ __device__ __forceinline__ void density_bwd_row4(B bins, const CouplingArgs &c, 
             float *gd_out = part == 0 ? gp + 2 * K : gud;
             if (on && inside) {
                 float g, gd[B::cap + 1], gk[B::cap];
-                const BinAdjoint a = rqs_bwd_core_any<false>(K, xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1),
-                                                             go, gl, g, gd);
-                knots_backward_any(K, kn, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
+                const BinAdjoint a = rqs_bwd_core<false>(bins, xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1),
+                                                         go, gl, g, nullptr, nullptr, gd);
+                knots_backward(bins, kn, nullptr, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
                 for (int k = 0; k < K; ++k) gk_out[k] = part == 0 ? gk[k] / c.sq : gk[k];
                 if (h == 0) {
                     gx[row * c.D + pos] = g;
@@ -1404,7 +1168,7 @@ __device__ __forceinline__ void sample_bwd_post_row(B bins, const CouplingArgs &
             const float *p = s.params + (row * c.n + j) * P;
             float w[B::cap], h[B::cap], gw[B::cap], gh[B::cap], gd[B::cap + 1];
             cond_params(bins, p, c.sq, w, h);
-            bins_point_bwd<true>(bins, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, adj_dst<B>(gd, gp + 2 * K));
+            rqs_point_bwd<true>(bins, xt, w, h, p + 2 * K, c.bound, got, gl, g, gw, gh, adj_dst<B>(gd, gp + 2 * K));
             FS_BINS_FOR(k, K, gp[k] = gw[k] / c.sq; gp[K + k] = gh[k] / c.sq;)
             if constexpr (B::fixed) FS_BINS_FOR(k, K + 1, gp[2 * K + k] = gd[k];)
         } else {
@@ -1437,7 +1201,7 @@ __device__ __forceinline__ void sample_bwd_pre_row(B bins, const CouplingArgs &c
         float g = gyi;
         if (zi >= -c.bound && zi <= c.bound) {
             float gw[B::cap], gh[B::cap], gd[B::cap + 1];
-            bins_point_bwd<true>(bins, zi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, gyi, gl, g,
+            rqs_point_bwd<true>(bins, zi, s.uw + j * K, s.uh + j * K, s.ud + j * (K + 1), c.bound, gyi, gl, g,
                                  adj_dst<B>(gw, guw), adj_dst<B>(gh, guh), adj_dst<B>(gd, gud));
             if constexpr (B::fixed) {
                 FS_BINS_FOR(k, K, guw[k] = gw[k]; guh[k] = gh[k];)
@@ -1493,76 +1257,80 @@ __global__ __launch_bounds__(256) void coupling_sample_bwd_step_kernel(CouplingA
 
 using namespace fs;
 
-#define FS_RQS_K(X) X(5) X(8) X(15) X(32)
+// launch(Bins<KT>{}) with the bin-count policy of (K, any_k): Bins<0> with any_k (K in the run-time
+// kernels' range; capi.cpp checks it with a message), else the instantiation for K;
+// hipErrorInvalidValue where there is none
+template <class F>
+static hipError_t with_bins(int K, bool any_k, F launch) {
+    if (any_k) {
+        if (K < 1 || K > kAnyMaxK) return hipErrorInvalidValue;
+        launch(Bins<0>{});
+    } else {
+        switch (K) {
+        case 5: launch(Bins<5>{}); break;
+        case 8: launch(Bins<8>{}); break;
+        case 15: launch(Bins<15>{}); break;
+        case 32: launch(Bins<32>{}); break;
+        default: return hipErrorInvalidValue;
+        }
+    }
+    return hipGetLastError();
+}
+#define FS_KT decltype(bins)::kt  // inside with_bins' launch(auto bins)
+
+static hipError_t rqs_forward_launch(bool any_k, int64_t M, int K, int inverse, const float *x, const float *uw,
+                                     const float *uh, const float *ud, float B, float *out, float *lad,
+                                     int32_t *nan_flag, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    return with_bins(K, any_k, [&](auto bins) {
+        if (inverse)
+            hipLaunchKernelGGL((rqs_forward_kernel<FS_KT, true>), grid, block, 0, st, M, x, uw, uh, ud, B, out, lad,
+                               nan_flag, K);
+        else
+            hipLaunchKernelGGL((rqs_forward_kernel<FS_KT, false>), grid, block, 0, st, M, x, uw, uh, ud, B, out, lad,
+                               nan_flag, K);
+    });
+}
+
+static hipError_t rqs_backward_launch(bool any_k, int64_t M, int K, int inverse, const float *x, const float *uw,
+                                      const float *uh, const float *ud, float B, const float *g_out,
+                                      const float *g_lad, float *gx, float *guw, float *guh, float *gud,
+                                      hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    return with_bins(K, any_k, [&](auto bins) {
+        if (inverse)
+            hipLaunchKernelGGL((rqs_backward_kernel<FS_KT, true>), grid, block, 0, st, M, x, uw, uh, ud, B, g_out,
+                               g_lad, gx, guw, guh, gud, K);
+        else
+            hipLaunchKernelGGL((rqs_backward_kernel<FS_KT, false>), grid, block, 0, st, M, x, uw, uh, ud, B, g_out,
+                               g_lad, gx, guw, guh, gud, K);
+    });
+}
 
 hipError_t fs_rqs_forward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
                                const float *ud, float B, float *out, float *lad, int32_t *nan_flag,
                                hipStream_t st) {
-    if (M <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
-#define FS_F(KK)                                                                                          \
-    if (K == KK) {                                                                                        \
-        if (inverse)                                                                                      \
-            hipLaunchKernelGGL((rqs_forward_kernel<KK, true>), grid, block, 0, st, M, x, uw, uh, ud, B, out, \
-                               lad, nan_flag);                                                            \
-        else                                                                                              \
-            hipLaunchKernelGGL((rqs_forward_kernel<KK, false>), grid, block, 0, st, M, x, uw, uh, ud, B, out, \
-                               lad, nan_flag);                                                            \
-        return hipGetLastError();                                                                         \
-    }
-    FS_RQS_K(FS_F)
-#undef FS_F
-    return hipErrorInvalidValue;
+    return rqs_forward_launch(false, M, K, inverse, x, uw, uh, ud, B, out, lad, nan_flag, st);
 }
 
 hipError_t fs_rqs_backward_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
                                 const float *ud, float B, const float *g_out, const float *g_lad, float *gx,
                                 float *guw, float *guh, float *gud, hipStream_t st) {
-    if (M <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
-#define FS_B(KK)                                                                                              \
-    if (K == KK) {                                                                                            \
-        if (inverse)                                                                                          \
-            hipLaunchKernelGGL((rqs_backward_kernel<KK, true>), grid, block, 0, st, M, x, uw, uh, ud, B, g_out, \
-                               g_lad, gx, guw, guh, gud);                                                     \
-        else                                                                                                  \
-            hipLaunchKernelGGL((rqs_backward_kernel<KK, false>), grid, block, 0, st, M, x, uw, uh, ud, B, g_out, \
-                               g_lad, gx, guw, guh, gud);                                                     \
-        return hipGetLastError();                                                                             \
-    }
-    FS_RQS_K(FS_B)
-#undef FS_B
-    return hipErrorInvalidValue;
+    return rqs_backward_launch(false, M, K, inverse, x, uw, uh, ud, B, g_out, g_lad, gx, guw, guh, gud, st);
 }
 
 hipError_t fs_rqs_forward_any_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
                                    const float *ud, float B, float *out, float *lad, int32_t *nan_flag,
                                    hipStream_t st) {
-    if (M <= 0) return hipSuccess;
-    if (K < 1 || K > kAnyMaxK) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
-    if (inverse)
-        hipLaunchKernelGGL(rqs_forward_any_kernel<true>, grid, block, 0, st, M, K, x, uw, uh, ud, B, out, lad,
-                           nan_flag);
-    else
-        hipLaunchKernelGGL(rqs_forward_any_kernel<false>, grid, block, 0, st, M, K, x, uw, uh, ud, B, out, lad,
-                           nan_flag);
-    return hipGetLastError();
+    return rqs_forward_launch(true, M, K, inverse, x, uw, uh, ud, B, out, lad, nan_flag, st);
 }
 
 hipError_t fs_rqs_backward_any_impl(int64_t M, int K, int inverse, const float *x, const float *uw, const float *uh,
                                     const float *ud, float B, const float *g_out, const float *g_lad, float *gx,
                                     float *guw, float *guh, float *gud, hipStream_t st) {
-    if (M <= 0) return hipSuccess;
-    if (K < 1 || K > kAnyMaxK) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
-    if (inverse)
-        hipLaunchKernelGGL(rqs_backward_any_kernel<true>, grid, block, 0, st, M, K, x, uw, uh, ud, B, g_out, g_lad,
-                           gx, guw, guh, gud);
-    else
-        hipLaunchKernelGGL(rqs_backward_any_kernel<false>, grid, block, 0, st, M, K, x, uw, uh, ud, B, g_out, g_lad,
-                           gx, guw, guh, gud);
-    return hipGetLastError();
+    return rqs_backward_launch(true, M, K, inverse, x, uw, uh, ud, B, g_out, g_lad, gx, guw, guh, gud, st);
 }
 
 // the training step's coupling launches on two / four waves per row (1, default, or
@@ -1603,25 +1371,11 @@ static fs::CouplingArgs coupling_args(const fs_coupling *c) {
 // any_k descriptors: K in the Bins<0> kernels' range (capi.cpp checks it with a message)
 static bool any_k_ok(const fs_coupling *c) { return c->K >= 1 && c->K <= kAnyMaxK; }
 
-// launch(Bins<KT>{}) with descriptor c's bin-count policy: Bins<0> with any_k, else the
-// instantiation for its K; hipErrorInvalidValue where there is none
+// with descriptor c's bin-count policy
 template <class F>
 static hipError_t with_bins(const fs_coupling *c, F launch) {
-    if (c->any_k) {
-        if (!any_k_ok(c)) return hipErrorInvalidValue;
-        launch(Bins<0>{});
-    } else {
-        switch (c->K) {
-        case 5: launch(Bins<5>{}); break;
-        case 8: launch(Bins<8>{}); break;
-        case 15: launch(Bins<15>{}); break;
-        case 32: launch(Bins<32>{}); break;
-        default: return hipErrorInvalidValue;
-        }
-    }
-    return hipGetLastError();
+    return with_bins(c->K, c->any_k != 0, launch);
 }
-#define FS_KT decltype(bins)::kt  // inside with_bins' launch(auto bins)
 
 // one wave per row (an any_k descriptor's K is refused before the 0-row return, an
 // uninstantiated K after it)

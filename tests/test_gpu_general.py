@@ -167,9 +167,9 @@ def test_multi_step_launch_matches_single_steps_in_general_mode():
     multi.check_errors()
 
 
-def _spline_case(K, inverse):
+def _spline_case(K, inverse, M=4096):
     g = torch.Generator().manual_seed(K + 7 * int(inverse))
-    M, B = 4096, 3.0
+    B = 3.0
     x = (torch.rand(M, generator=g) * 2 - 1) * B * 1.05  # ~5 % outside
     x[:4] = torch.tensor([B, -B, 0.0, B * 1.2])
     uw = torch.randn(M, K, generator=g) * 0.7
@@ -235,11 +235,11 @@ def test_runtime_k_spline_forward_inverse_consistent(K):
 
 
 @pytest.mark.parametrize("inverse", [False, True])
-def test_runtime_k_entry_points_match_instantiated_kernels(inverse):
-    """K = 8 through fs_rqs_forward_any / fs_rqs_backward_any against fs_rqs_forward /
-    fs_rqs_backward on the same operands."""
-    K = 8
-    B, x, uw, uh, ud, wo, wl = (t.cuda() if torch.is_tensor(t) else t for t in _spline_case(K, inverse))
+@pytest.mark.parametrize("K", [5, 8, 15, 32])
+def test_runtime_k_entry_points_match_instantiated_kernels(K, inverse):
+    """Every instantiated K through fs_rqs_forward_any / fs_rqs_backward_any against fs_rqs_forward /
+    fs_rqs_backward on the same operands (M = 1000: a ragged last workgroup)."""
+    B, x, uw, uh, ud, wo, wl = (t.cuda() if torch.is_tensor(t) else t for t in _spline_case(K, inverse, M=1000))
     lib, p, st = _lib.load(), _lib.ptr, _lib.stream_ptr()
     M = x.numel()
     res = {}

@@ -102,6 +102,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--no-launches", action="store_true", help="timings only: skip the launch count")
     a = ap.parse_args()
     cases = a.cases.split(",")
     B = half_box(N)
@@ -138,6 +139,8 @@ def main():
     if "b" in res and "c" in res:
         out["runtime_k_over_instantiated"] = res["c"]["steps_per_s"] / res["b"]["steps_per_s"]
     print(json.dumps(out), flush=True)
+    if a.no_launches:
+        return
     for c in cases:
         AF._force_any_k = CASES[c][2]
         try:
