@@ -806,6 +806,13 @@ struct WideArgs {
                     // once (the timeout test hook, fs_set_wide_handoff_spins)
 };
 
+template <int H>
+struct WideStride {
+    static constexpr int XS = (H < 2 * kMaxN ? 2 * kMaxN : H) + 4;  // XA / XB row stride
+    static constexpr int XS16 = XS + 4;  // a 16-row tile's LDS image (== 8 mod 64: t16_pos)
+    static_assert(XS16 % 64 == 8, "trunk16 LDS row stride");
+};
+
 template <int MODE>
 __global__ void __launch_bounds__(256) wide_input_kernel(WideArgs w) {
     const FlowArgs &a = w.a;
@@ -874,7 +881,7 @@ __device__ __forceinline__ float wide_fold(const WideArgs &w, int64_t row, int v
 // then the periodic features of the layer -> XA.  One workgroup of 8 waves per 64 rows.
 template <int H, int K, int MODE>
 __global__ void __launch_bounds__(kThreads) wide_start_kernel(WideArgs w) {
-    constexpr int XS = (H < 2 * kMaxN ? 2 * kMaxN : H) + 4;
+    constexpr int XS = WideStride<H>::XS;
     const FlowArgs &a = w.a;
     const int N = a.N, D = 2 * N;
     const PackLayout PL = pack_layout(N, H, a.nb, a.K);
@@ -908,7 +915,7 @@ __global__ void __launch_bounds__(kThreads) wide_start_kernel(WideArgs w) {
 // writing the final layer's input h + s_h to XB.
 template <int H>
 __global__ void __launch_bounds__(64 * (H / 32)) wide_trunk_kernel(WideArgs w) {
-    constexpr int XS = (H < 2 * kMaxN ? 2 * kMaxN : H) + 4;
+    constexpr int XS = WideStride<H>::XS;
     __shared__ __attribute__((aligned(16))) float X[32 * XS];
     const FlowArgs &a = w.a;
     const int N = a.N;
@@ -972,133 +979,11 @@ __device__ __forceinline__ f32x2 ldb_pair(__amdgpu_buffer_rsrc_t W, int voff, in
     return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(W, voff, soff, 0));
 }
 
-// acc[c] (16 x 16, columns 32 tile + 16 c ..) = X[16 x 8 kg] . B[tile], ACC: onto acc
-template <int XS16, int PD, bool ACC>
-__device__ __forceinline__ void gemm16(const float *__restrict__ X, __amdgpu_buffer_rsrc_t W, int sec, int kg,
-                                       int tile, f32x4 (&acc)[2]) {
-    const int lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15, h = lane >> 5, qo = q & 1;
-    if (!ACC)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[c][i] = 0.f;
-    const float *xa = X + r * XS16 + 4 * qo + ((2 * h) ^ (((r >> 3) & 1) << 1));
-    const int vb = (32 * qo + r) * 16 + 8 * h;  // + 256 c: the second 16-column half
-    const int fb = sec + tile * kg * 1024;
-    // both operands in PD-deep rings: the weights from L2 / MALL, the activation pairs from
-    // LDS (an LDS read issued right before its MFMAs would stall every k-group)
-    f32x2 rb[PD][2], ra[PD];
-#pragma unroll
-    for (int s = 0; s < PD; ++s)
-        if (s < kg) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) rb[s][c] = ldb_pair(W, vb + 256 * c, fb + s * 1024);
-            ra[s] = *(const f32x2 *)(xa + 8 * s);
-        }
-    for (int g0 = 0; g0 < kg; g0 += PD) {
-#pragma unroll
-        for (int s = 0; s < PD; ++s) {
-            const int g = g0 + s;
-            if (g < kg) {
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-                        acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(ra[s][m], rb[s][c][m], acc[c], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                const int gn = g + PD;
-                if (gn < kg) {
-                    ra[s] = *(const f32x2 *)(xa + 8 * gn);
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) rb[s][c] = ldb_pair(W, vb + 256 * c, fb + gn * 1024);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-}
-
-#ifndef FS_WIDE16_PD
-#define FS_WIDE16_PD 24  // k-groups in flight (2 loads each): the weights stream from MALL / HBM
-#endif
-
-// wide_trunk_kernel on a 16-row tile: one wave per 32-column tile (two 16x16 halves), the
-// same GEMMs, epilogues (FS_EPI), deferred biases and residual stream, bit for bit
-template <int H>
-struct Trunk16 {
-    static constexpr int XS = (H < 2 * kMaxN ? 2 * kMaxN : H) + 4;  // XA / XB row stride
-    static constexpr int XS16 = XS + 4;                             // the LDS image's (== 8 mod 64)
-    static_assert(XS16 % 64 == 8, "trunk16 LDS row stride");
-};
-
-// the trunk of one 16-row tile whose features are in the LDS image X (t16_pos layout); a
-// launch of NW > H / 32 waves leaves the extra ones to the barriers
-template <int H, int NW = H / 32>
-__device__ __forceinline__ void trunk16_run(float *X, const WideArgs &w, int64_t rowt) {
-    constexpr int XS = Trunk16<H>::XS, XS16 = Trunk16<H>::XS16;
-    const FlowArgs &a = w.a;
-    const int N = a.N;
-    const PackLayout PL = pack_layout(N, H, a.nb, a.K);
-    const int lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
-    const int tile = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool act = NW == H / 32 || tile < H / 32;
-    const float *P = a.packed + (int64_t)w.layer * PL.stride;
-    const float *V = P + PL.vec;
-    const __amdgpu_buffer_rsrc_t W =
-        __builtin_amdgcn_make_buffer_rsrc((void *)P, (short)0, (int)(PL.stride * 4), 0x00020000);
-    int col[2], pos[2][4];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        col[c] = act ? 32 * tile + 16 * c + r : 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pos[c][i] = t16_pos(4 * q + i, col[c], XS16);
-    }
-    f32x4 hr[2], acc[2];
-    if (act) gemm16<XS16, FS_WIDE16_PD, false>(X, W, (int)(PL.win * 4), PL.kg_in, tile, hr);  // initial_layer
-    for (int jb = 0; jb < a.nb; ++jb) {  // ResidualBlock (resnet.py:37-50), eval BN folded
-        const float *VB = V + PL.v_blocks + (int64_t)4 * H * jb;
-        float e0[2], e1[2], e2[2], e3[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            e0[c] = VB[col[c]];
-            e1[c] = VB[H + col[c]];
-            e2[c] = VB[2 * H + col[c]];
-            e3[c] = VB[3 * H + col[c]];
-        }
-        const int w0 = (int)((PL.blocks + jb * PL.block_stride) * 4);
-        __syncthreads();
-        if (act)
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) X[pos[c][i]] = FS_EPI(hr[c][i], e0[c], e1[c]);
-        __syncthreads();
-        if (act) gemm16<XS16, FS_WIDE16_PD, false>(X, W, w0, PL.kg_h, tile, acc);
-        __syncthreads();
-        if (act)
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) X[pos[c][i]] = FS_EPI(acc[c][i], e2[c], e3[c]);
-        __syncthreads();
-        if (act) gemm16<XS16, FS_WIDE16_PD, true>(X, W, w0 + (int)(PL.block_stride * 2), PL.kg_h, tile, hr);  // h += Lin1(t)
-    }
-    if (!act) return;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const float sh = V[col[c]];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w.XB[(rowt + 4 * q + i) * XS + col[c]] = hr[c][i] + sh;
-    }
-}
-
-// The 16-row trunk with each 32-column tile split over two waves, one 16-column half each
-// (wide_trunk16s_kernel, trunk16 = 3, the default).  trunk16_run's waves were parked on
-// their weight loads and barriers ~40 % of the time with two waves per SIMD (r05 PMC:
-// SQ_VALU_MFMA_BUSY 0.61 of SIMD cycles); halving each wave's tile doubles the waves per SIMD
-// that hide those waits, and at H = 128 the merged kernel's 8 waves all run the trunk instead
-// of 4.  A half's accumulator takes the same MFMAs in the same order as gemm16's acc[c]
-// (per k-group m = 0 then 1), so the results are bit-identical.
+// The 16-row trunk runs each 32-column tile on two waves, one 16-column half (c) each: 2 H / 32
+// half-tile waves per row tile (wide_trunk16s_kernel, trunk16 = 3; over several workgroups,
+// wide_trunk16g_kernel, 4).  A half's accumulator takes per k-group the MFMAs m = 0 then 1,
+// the 32-row tile's chain for those columns, so the results are bit-identical.  (The form
+// with one wave per 32-column tile, retired: DESIGN_HISTORY.md.)
 // The weight half of gemm16h's ring prologue, issued before the epilogue and barrier that
 // precede the GEMM (its loads do not depend on the activations).  (Loading the next block's
 // epilogue vectors a GEMM early lost 2-3 %, r05j.)
@@ -1161,85 +1046,54 @@ __device__ __forceinline__ void gemm16h(const float *__restrict__ X, __amdgpu_bu
 #endif
 
 
-// trunk16_run with wave w computing half (w & 1) of column tile w >> 1 (2 H / 32 trunk waves).
+// The trunk of one 16-row tile whose features are in the LDS image X (t16_pos layout), by the
+// tile's 2 H / 32 half-tile waves: wave wv computes half (wv & 1) of column tile wv >> 1.
+// wide_trunk_kernel's GEMMs, epilogues (FS_EPI), deferred biases and residual stream, bit for bit.
 // The activation image is double-buffered (X: the features, then every other epilogue; Y: the
 // rest), so an epilogue never overwrites the image the GEMM before it read: one barrier per
 // epilogue (its writes before the next GEMM's reads) instead of two.
-template <int H, int NW = 2 * (H / 32)>
+template <int H>
 __device__ __forceinline__ void trunk16h_run(float *X, float *Y, const WideArgs &w, int64_t rowt) {
-    constexpr int XS = Trunk16<H>::XS, XS16 = Trunk16<H>::XS16;
+    constexpr int XS = WideStride<H>::XS, XS16 = WideStride<H>::XS16;
     const FlowArgs &a = w.a;
     const int N = a.N;
     const PackLayout PL = pack_layout(N, H, a.nb, a.K);
     const int lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tile = wv >> 1, c = wv & 1;
-    const bool act = NW == 2 * (H / 32) || wv < 2 * (H / 32);
     const float *P = a.packed + (int64_t)w.layer * PL.stride;
     const float *V = P + PL.vec;
     const __amdgpu_buffer_rsrc_t W =
         __builtin_amdgcn_make_buffer_rsrc((void *)P, (short)0, (int)(PL.stride * 4), 0x00020000);
-    const int col = act ? 32 * tile + 16 * c + r : 0;
+    const int col = 32 * tile + 16 * c + r;
     int pos[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) pos[i] = t16_pos(4 * q + i, col, XS16);
     f32x4 hr, acc;
     f32x2 rb[FS_WIDE16H_PD];
-    if (act) {
-        gemm16h_pre<FS_WIDE16H_PD>(W, (int)(PL.win * 4), PL.kg_in, tile, c, rb);
-        gemm16h<XS16, FS_WIDE16H_PD, FS_WIDE16H_XB, false>(X, W, (int)(PL.win * 4), PL.kg_in, tile, c, hr, rb);  // initial_layer
-    }
+    gemm16h_pre<FS_WIDE16H_PD>(W, (int)(PL.win * 4), PL.kg_in, tile, c, rb);
+    gemm16h<XS16, FS_WIDE16H_PD, FS_WIDE16H_XB, false>(X, W, (int)(PL.win * 4), PL.kg_in, tile, c, hr, rb);  // initial_layer
     for (int jb = 0; jb < a.nb; ++jb) {  // ResidualBlock (resnet.py:37-50), eval BN folded
         const float *VB = V + PL.v_blocks + (int64_t)4 * H * jb;
         const float e0 = VB[col], e1 = VB[H + col], e2 = VB[2 * H + col], e3 = VB[3 * H + col];
         const int w0 = (int)((PL.blocks + jb * PL.block_stride) * 4), w1 = w0 + (int)(PL.block_stride * 2);
         // Y was last read by the previous block's first GEMM (or never): every wave has passed
         // the barrier after it, so these writes need no barrier before them
-        if (act) {
-            gemm16h_pre<FS_WIDE16H_PD>(W, w0, PL.kg_h, tile, c, rb);  // ahead of the barrier
+        gemm16h_pre<FS_WIDE16H_PD>(W, w0, PL.kg_h, tile, c, rb);  // ahead of the barrier
 #pragma unroll
-            for (int i = 0; i < 4; ++i) Y[pos[i]] = FS_EPI(hr[i], e0, e1);
-        }
+        for (int i = 0; i < 4; ++i) Y[pos[i]] = FS_EPI(hr[i], e0, e1);
         __syncthreads();
-        if (act) {
-            gemm16h<XS16, FS_WIDE16H_PD, FS_WIDE16H_XB, false>(Y, W, w0, PL.kg_h, tile, c, acc, rb);
-            gemm16h_pre<FS_WIDE16H_PD>(W, w1, PL.kg_h, tile, c, rb);
-        }
+        gemm16h<XS16, FS_WIDE16H_PD, FS_WIDE16H_XB, false>(Y, W, w0, PL.kg_h, tile, c, acc, rb);
+        gemm16h_pre<FS_WIDE16H_PD>(W, w1, PL.kg_h, tile, c, rb);
         // X was last read by the GEMM before the barrier above (initial layer / second GEMM)
-        if (act)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) X[pos[i]] = FS_EPI(acc[i], e2, e3);
+        for (int i = 0; i < 4; ++i) X[pos[i]] = FS_EPI(acc[i], e2, e3);
         __syncthreads();
-        if (act) {
-            gemm16h<XS16, FS_WIDE16H_PD, FS_WIDE16H_XB, true>(X, W, w1, PL.kg_h, tile, c, hr, rb);  // h += Lin1(t)
-        }
+        gemm16h<XS16, FS_WIDE16H_PD, FS_WIDE16H_XB, true>(X, W, w1, PL.kg_h, tile, c, hr, rb);  // h += Lin1(t)
     }
-    if (!act) return;
     const float sh = V[col];
 #pragma unroll
     for (int i = 0; i < 4; ++i) w.XB[(rowt + 4 * q + i) * XS + col] = hr[i] + sh;
-}
-
-template <int H>
-__global__ void __launch_bounds__(64 * (H / 32)) wide_trunk16_kernel(WideArgs w) {
-    constexpr int XS = Trunk16<H>::XS, XS16 = Trunk16<H>::XS16;
-    __shared__ __attribute__((aligned(16))) float X[16 * XS16];
-    const PackLayout PL = pack_layout(w.a.N, H, w.a.nb, w.a.K);
-    const int64_t rowt = (int64_t)blockIdx.x * 16;
-    const int nq = 2 * PL.kg_in;  // 16-byte quads of the used feature columns
-    for (int e = threadIdx.x; e < 16 * nq; e += blockDim.x) {
-        const int rr = e / nq, qq = e - rr * nq;
-        const f32x4 v = *(const f32x4 *)(w.XA + (rowt + rr) * XS + 4 * qq);
-        f32x4 o;  // positions of columns (0, 1, 2, 3): (0, 2, 1, 3), bit 1 flipped in rows 8-15
-        if (rr < 8) {
-            o[0] = v[0]; o[1] = v[2]; o[2] = v[1]; o[3] = v[3];
-        } else {
-            o[0] = v[1]; o[1] = v[3]; o[2] = v[0]; o[3] = v[2];
-        }
-        *(f32x4 *)(X + rr * XS16 + 4 * qq) = o;
-    }
-    __syncthreads();
-    trunk16_run<H>(X, w, rowt);
 }
 
 // One feature of uncond_spline_w at the value x: its log-det returned and the new value in
@@ -1299,7 +1153,7 @@ __device__ __forceinline__ float uncond_one(const float *__restrict__ U, float *
 // previous layer (its slot is the other buffer) and the feature padding.
 template <int H, int K, int MODE>
 __global__ void __launch_bounds__(kThreads) wide_start_s_kernel(WideArgs w) {
-    constexpr int XS = (H < 2 * kMaxN ? 2 * kMaxN : H) + 4;
+    constexpr int XS = WideStride<H>::XS;
     const FlowArgs &a = w.a;
     const int N = a.N, D = 2 * N;
     const PackLayout PL = pack_layout(N, H, a.nb, a.K);
@@ -1338,17 +1192,12 @@ __global__ void __launch_bounds__(kThreads) wide_start_s_kernel(WideArgs w) {
 // and the XA round trip.  Sampling modes write CO, LDU / LDU2 and LDW as
 // wide_start_s_kernel does, density LDW as wide_start_kernel: the same device code on the
 // same operands, so the pass stays bit-identical (tests/test_gpu_wide.py).
-template <int H, bool HALF = false>
-constexpr int trunk16s_waves() {  // twice the trunk's waves (the start's splines) up to 8; HALF: two per tile
-    return HALF ? 2 * (H / 32) : (2 * (H / 32) < 8 ? 2 * (H / 32) : (H / 32 > 8 ? H / 32 : 8));
-}
-
-template <int H, int K, int MODE, bool HALF = false>
-__global__ void __launch_bounds__((64 * trunk16s_waves<H, HALF>())) wide_trunk16s_kernel(WideArgs w) {
-    constexpr int XS16 = Trunk16<H>::XS16;
+template <int H, int K, int MODE>
+__global__ void __launch_bounds__(64 * 2 * (H / 32)) wide_trunk16s_kernel(WideArgs w) {
+    constexpr int XS16 = WideStride<H>::XS16;
     __shared__ __attribute__((aligned(16))) float X[16 * XS16];
     __shared__ float TU[MODE != MODE_DENSITY ? kMaxN * 3 * (K + 1) : 1];  // unconditional spline tables
-    __shared__ __attribute__((aligned(16))) float Y[HALF ? 16 * XS16 : 4];  // trunk16h_run's second image
+    __shared__ __attribute__((aligned(16))) float Y[16 * XS16];           // trunk16h_run's second image
     const FlowArgs &a = w.a;
     const int N = a.N, D = 2 * N;
     const PackLayout PL = pack_layout(N, H, a.nb, a.K);
@@ -1370,7 +1219,7 @@ __global__ void __launch_bounds__((64 * trunk16s_waves<H, HALF>())) wide_trunk16
     float *lu_cur = (w.layer & 1) ? w.LDU2 : w.LDU;
     // every thread's coordinates first (independent loads in flight together), the
     // sampling modes' spline tables staged in LDS (one coalesced pass), then the features
-    constexpr int NW = trunk16s_waves<H, HALF>(), NT = 64 * NW, IT = (16 * kMaxN + NT - 1) / NT;
+    constexpr int NT = 64 * 2 * (H / 32), IT = (16 * kMaxN + NT - 1) / NT;
     float xv[IT];
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
@@ -1407,10 +1256,7 @@ __global__ void __launch_bounds__((64 * trunk16s_waves<H, HALF>())) wide_trunk16
         X[t16_pos(rr, D + e - rr * npad, XS16)] = 0.f;
     }
     __syncthreads();
-    if constexpr (HALF)
-        trunk16h_run<H, NW>(X, Y, w, rowt);
-    else
-        trunk16_run<H, NW>(X, w, rowt);
+    trunk16h_run<H>(X, Y, w, rowt);
 }
 
 // ---------------------------------------------------------------------------
@@ -1456,7 +1302,7 @@ constexpr bool gsplit_ok() {
 
 template <int H, int K, int MODE, int G>
 __global__ void __launch_bounds__(64 * (2 * (H / 32) / G)) wide_trunk16g_kernel(WideArgs w) {
-    constexpr int XS = Trunk16<H>::XS, XS16 = Trunk16<H>::XS16;
+    constexpr int XS = WideStride<H>::XS, XS16 = WideStride<H>::XS16;
     constexpr int NW = 2 * (H / 32) / G, NT = 64 * NW;  // waves / threads per workgroup
     constexpr int CPG = H / G;                          // columns per workgroup
     static_assert(NW >= 1 && NW * G == 2 * (H / 32), "G divides the trunk's half-tile waves");
@@ -1633,7 +1479,7 @@ __global__ void __launch_bounds__(64 * WPB) wide_final_kernel(WideArgs w) {
     // chip idle (or, K > 16, at two workgroups per CU); each chain's spline runs in both lane
     // halves, the lower one stores
     static_assert(RB == kRows || RB == 32, "64- or 32-row final blocks");
-    constexpr int XS = (H < 2 * kMaxN ? 2 * kMaxN : H) + 4;
+    constexpr int XS = WideStride<H>::XS;
     constexpr int RM = RB - 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *X = (float *)smem;
@@ -1781,7 +1627,7 @@ __device__ __forceinline__ void final_pair16(const float *__restrict__ X, __amdg
 template <int H, int K, int MODE, int WPB>
 __global__ void __launch_bounds__(64 * WPB) wide_final16_kernel(WideArgs w) {
     static_assert(K <= 16, "16-row final blocks: feature pairs only");
-    constexpr int XS = (H < 2 * kMaxN ? 2 * kMaxN : H) + 4;
+    constexpr int XS = WideStride<H>::XS;
     constexpr bool INV = MODE != MODE_DENSITY;
     constexpr int TS = INV ? 1 : 0;
     __shared__ __attribute__((aligned(16))) float X[16 * XS];
@@ -2126,18 +1972,21 @@ static int device_cus() {
     return v;
 }
 
-// the trunk on 16-row tiles with the layer's start merged in and each 32-column tile split
-// over two waves (wide_trunk16s_kernel<..., true>, 3, the default), the same with one wave per
-// tile (2), on 16-row tiles after a separate start launch (1) or on 32-row ones (0);
-// FS_WIDE_TRUNK16, fs_set_wide_trunk16.  Bit-identical in every setting.
+// the trunk on 16-row tiles with the layer's start merged in: the column-split trunk for small
+// batches of the A1 trunk, else one workgroup per tile (5, the default; wide_pass_t), the
+// column-split trunk wherever it fits (4), one workgroup per tile (wide_trunk16s_kernel, 3);
+// or on 32-row tiles after a separate start launch (0).  1 and 2, earlier forms of the 16-row
+// trunk, are retired aliases of 3 and stored as 3.  FS_WIDE_TRUNK16, fs_set_wide_trunk16.
+// Bit-identical in every setting.
 static std::atomic<int> g_trunk16{-1};
 static std::atomic<unsigned> g_gspin{kGSpinMax};
+static int trunk16_setting(int v) { return v > 5 ? 5 : (v == 1 || v == 2) ? 3 : v; }
 static int wide_trunk16() {
     int v = g_trunk16.load(std::memory_order_relaxed);
     if (v < 0) {
         const char *e = getenv("FS_WIDE_TRUNK16");
         int expect = -1;
-        g_trunk16.compare_exchange_strong(expect, (e && e[0] >= '0' && e[0] <= '5') ? e[0] - '0' : 5);
+        g_trunk16.compare_exchange_strong(expect, (e && e[0] >= '0' && e[0] <= '5') ? trunk16_setting(e[0] - '0') : 5);
         v = g_trunk16.load(std::memory_order_relaxed);
     }
     return v;
@@ -2293,7 +2142,7 @@ static hipError_t wide_pass_t(const FlowArgs &a, int N, hipStream_t st, bool &us
     if (wide_bytes(R, N, H) > cap) return hipSuccess;
     char *p = (char *)wide_workspace(cap, st);
     if (!p) return hipSuccess;
-    constexpr int XS = (H < 2 * kMaxN ? 2 * kMaxN : H) + 4;
+    constexpr int XS = WideStride<H>::XS;
     const int D = 2 * N;
     WideArgs w;
     memset(&w, 0, sizeof(w));
@@ -2373,18 +2222,12 @@ static hipError_t wide_pass_t(const FlowArgs &a, int N, hipStream_t st, bool &us
                     dim3(FS_GSPLIT_XCD ? (unsigned)((R / 16 + 7) / 8) * 8 * FS_GSPLIT : (unsigned)(R / 16) * FS_GSPLIT),
                     dim3(64 * (2 * (H / 32) / FS_GSPLIT)), 0);
         } else if (trunk16 == 3)
-            add((const void *)wide_trunk16s_kernel<H, K, MODE, true>, dim3((unsigned)(R / 16)),
-                dim3(64 * trunk16s_waves<H, true>()), 0);
-        else if (trunk16 == 2)
-            add((const void *)wide_trunk16s_kernel<H, K, MODE>, dim3((unsigned)(R / 16)), dim3(64 * trunk16s_waves<H>()),
-                0);
+            add((const void *)wide_trunk16s_kernel<H, K, MODE>, dim3((unsigned)(R / 16)), dim3(64 * 2 * (H / 32)), 0);
         else if (MODE == MODE_DENSITY)
             add((const void *)wide_start_kernel<H, K, MODE>, dim3(nblk), dim3(kThreads), 0);
         else
             add((const void *)wide_start_s_kernel<H, K, MODE>, dim3(nblk, kWaves), dim3(kThreads), 0);
-        if (trunk16 == 1)
-            add((const void *)wide_trunk16_kernel<H>, dim3((unsigned)(R / 16)), dim3(64 * (H / 32)), 0);
-        else if (trunk16 == 0)
+        if (trunk16 == 0)
             add((const void *)wide_trunk_kernel<H>, dim3((unsigned)(R / 32)), dim3(64 * (H / 32)), 0);
         if (frows == 16)
             add(final_fn, dim3((unsigned)(R / 16), fgy), dim3(64 * WPW), 0);
@@ -2418,7 +2261,7 @@ using namespace fs;
 
 int32_t fs_set_wide_trunk16_impl(int32_t on) {
     const int32_t prev = wide_trunk16();
-    if (on >= 0) g_trunk16.store(on > 5 ? 5 : on, std::memory_order_relaxed);
+    if (on >= 0) g_trunk16.store(trunk16_setting(on), std::memory_order_relaxed);
     return prev;
 }
 

@@ -303,8 +303,9 @@ int64_t fs_general_wide_passes(void);
  *   the tiles x 4 fit half the chip, else 3; err |= 4 if a hand-off wait gave up); 3 = the
  *   wide path's ResidualNet on 16-row tiles (v_mfma_f32_16x16x4_f32, twice the workgroups)
  *   with each layer's start phase merged into the trunk launch and each 32-column tile split
- *   over two waves (one 16-column half each), 2 = the same with one wave per tile, 1 = 16-row
- *   tiles after a separate start launch, 0 = 32-row tiles.
+ *   over two waves (one 16-column half each), 0 = 32-row tiles after a separate start launch.
+ *   1 and 2 selected earlier forms of the 16-row trunk, since removed: they are accepted as
+ *   aliases of 3, and stored and returned as 3.  Values above 5 are stored as 5.
  * fs_set_wide_final32: 2 (default, or FS_WIDE_FINAL32) = the wide path's final phase on
  *   16- or 32-row blocks when that grid fits the chip in one round (16-row blocks on
  *   v_mfma_f32_16x16x4_f32 for spline bins K <= 16 only; K > 16, one feature per wave:

@@ -186,9 +186,9 @@ def _all_equal(runs):
 @pytest.mark.parametrize("shape", FC.SHAPES, ids=_id)
 def test_f32_paths_bit_identical_on_sharp_weights(shape):
     """The wide path, its trunk variants (5: by batch size, 4: the column-split trunk, which
-    200 rows may take, 3, 2, 1, 0) and its final-phase variants (2, 1, 0) against the fused
-    kernel, density and sampling, on the sharp case's own rows (boundary and outside rows
-    included)."""
+    200 rows may take, 3 and its retired aliases 2 and 1, 0) and its final-phase variants
+    (2, 1, 0) against the fused kernel, density and sampling, on the sharp case's own rows
+    (boundary and outside rows included)."""
     _, _, ref, _, _ = FC.case(shape)
     m = model(shape, "f32")
     x, z0 = ref.x.cuda(), ref.z0.cuda()

@@ -130,8 +130,8 @@ class trunk16:
     """The wide path's trunk for a block: by batch size (5, the default: 4 for small batches,
     else 3), each 16-row tile's columns split over several workgroups with in-launch hand-offs
     (4, where the tiles fit half the chip, else 3), 16-row tiles with the layer's start merged
-    in and two waves per 32-column tile (3), the same with one wave per tile (2), 16-row tiles
-    after a start launch (1) or 32-row tiles (0)."""
+    in and two waves per 32-column tile (3) or 32-row tiles after a start launch (0).  1 and 2,
+    earlier forms of the 16-row trunk, are retired aliases of 3."""
 
     def __init__(self, on):
         self.on = on
@@ -144,12 +144,15 @@ class trunk16:
 
 
 @pytest.mark.parametrize("N,kw,B", [(64, A1, 1000), (16, A1, 4096), (64, A2, 200), (3, dict(L=2, H=32, nb=2, K=5), 77),
-                                    (16, dict(L=3, H=64, nb=2, K=8), 130)],
-                         ids=["a1-n64-1000", "a1-n16-4096", "a2-n64-200", "n3-h32-77", "n16-h64-130"])
+                                    (16, dict(L=3, H=64, nb=2, K=8), 130), (64, dict(L=2, H=64, nb=2, K=8), 17)],
+                         ids=["a1-n64-1000", "a1-n16-4096", "a2-n64-200", "n3-h32-77", "n16-h64-130", "n64-h64-17"])
 def test_trunk16_bit_identical_to_trunk32(N, kw, B):
-    """The 16-row trunk (v_mfma_f32_16x16x4_f32 fed the 32x32x2 k order), with the start
-    merged in (one or two waves per column tile) and without, against the 32-row one,
-    density and sampling, and all against the fused kernel."""
+    """The 16-row trunk (v_mfma_f32_16x16x4_f32 fed the 32x32x2 k order) with the start merged
+    in, on one workgroup per tile (3, and its retired aliases 2 and 1) and column-split (4, 5),
+    against the 32-row one, density and sampling, and all against the fused kernel.
+    n64-h64-17: the narrowest width the column-split trunk takes (one wave per workgroup), so
+    each thread walks all 16 steps of the start's per-thread loop and of the deferred flush;
+    17 rows are a full tile, a ragged one and two of padding."""
     dims, sd, m = _model(N, kw, seed=11)
     g = torch.Generator().manual_seed(B)
     x = ((torch.rand((B, dims.D), generator=g) * 2 - 1) * dims.B).cuda()
@@ -208,8 +211,9 @@ def test_final32_bit_identical_to_final64(N, kw, B):
         assert torch.equal(a, b) and torch.equal(a, c) and torch.equal(a, d)
 
 
-@pytest.mark.parametrize("N,kw,B", [(16, A1, 100), (3, dict(L=3, H=128, nb=2, K=32), 10), (64, A2, 500)],
-                         ids=["a1-n16-100", "n3-h128-10", "a2-n64-500"])
+@pytest.mark.parametrize("N,kw,B", [(16, A1, 100), (3, dict(L=3, H=128, nb=2, K=32), 10), (64, A2, 500),
+                                    (64, dict(L=2, H=64, nb=2, K=8), 17)],
+                         ids=["a1-n16-100", "n3-h128-10", "a2-n64-500", "n64-h64-17"])
 def test_column_split_trunk_hand_offs_complete(N, kw, B):
     """The column-split trunk (4): every in-launch hand-off completes (err word 0, no bounded
     poll gave up) across density and propose passes replayed back to back (the counters are

@@ -255,6 +255,22 @@ def test_column_split_xcd_placement_is_a_bijection():
             assert len({seen[(t, g)] % 8 for g in range(G)}) == 1
 
 
+def test_wide_trunk16_retired_settings_are_aliases_of_3():
+    """fs_set_wide_trunk16: 1 and 2 (earlier forms of the 16-row trunk) are stored and read back
+    as 3; 0, 3, 4, 5 as set; above 5 is 5; a negative argument only reads."""
+    L = _lib.load()
+    orig = L.fs_set_wide_trunk16(-1)
+    try:
+        for on, want in ((2, 3), (1, 3), (0, 0), (3, 3), (4, 4), (5, 5), (9, 5)):
+            L.fs_set_wide_trunk16(on)
+            assert L.fs_set_wide_trunk16(-1) == want
+            assert L.fs_set_wide_trunk16(-1) == want  # reading changed nothing
+        assert L.fs_set_wide_trunk16(1) == 5  # the previous value is returned
+    finally:
+        L.fs_set_wide_trunk16(orig)
+    assert L.fs_set_wide_trunk16(-1) == orig
+
+
 def test_pipeline_schedule():
     """algorithm1.pipeline_schedule: every stage after the first runs ahead; an accept in
     big move j sends stage j+1 back to the main stream (its next stage runs ahead again from
