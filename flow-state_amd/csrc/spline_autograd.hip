@@ -5,10 +5,11 @@
 //
 // Forward: unconstrained_rational_quadratic_spline, circular-tail branch
 // (NF/normflows/utils/splines.py:16-88) + rational_quadratic_spline (:91-222): identity
-// and log-det 0 outside [-B, B]; inside: softmax -> min-width affine -> cumsum
-// (double accumulation, as torch CPU) -> [-B, B] with pinned ends; derivatives
-// 1e-3 + softplus; searchsorted with the eps on the last knot; the rational-quadratic
-// map (forward) or its quadratic-root inverse, and the log|det|.
+// and log-det 0 outside [-B, B]; inside: softmax -> min-width affine -> cumsum -> [-B, B]
+// with pinned ends (all in double from the float exponentials on, each knot rounded once);
+// derivatives 1e-3 + softplus; searchsorted with the eps on the last knot; the
+// rational-quadratic map (forward) or its quadratic-root inverse (the root in its
+// cancellation-free form, pinned to [0, 1]), and the log|det|.
 // Backward: reverse-mode by hand.  Forward direction: through theta = (x - cw_b)/w_b.
 // Inverse direction: the root theta* solves F(theta) = y, so its adjoint reaches y and
 // the knot values through -F_q / F_theta (implicit function theorem).  Knot adjoints go
@@ -43,13 +44,10 @@ constexpr float kMin = 1e-3f;  // DEFAULT_MIN_BIN_WIDTH / HEIGHT / DERIVATIVE (s
 // function and kernel is written once over it.  With a compile-time K the loops over the bins
 // unroll whole and the per-thread arrays stay registers; with a run-time K they have kAnyMaxK
 // entries in private memory and the loops run to K.  What else differs lies behind
-// `if constexpr (B::fixed)`: how a bin's knots are read (pick_bin), whether the knot adjoints are
-// kept dense or sparse (rqs_bwd_core, knots_backward), where the adjoints are stored (adj_dst), and
-// both shapes of one statement sequence in knots_pair and density_bwd_row4.  All of this is
-// arranged so that every instantiation compiles to the instruction stream it had when the two
-// families were separate copies ('General-shape mode'): same operations in the same
-// order, so at K in {5, 8, 15, 32} Bins<0> gives what Bins<K> gives up to the compiler's choice of
-// instructions.
+// `if constexpr (B::fixed)`: how a bin's knots are read (pick_bin), where the adjoints are stored
+// (adj_dst), and both shapes of one statement sequence in knots_pair and density_bwd_row4.  Both
+// policies do the same operations in the same order ('General-shape mode'), so at K in
+// {5, 8, 15, 32} Bins<0> gives what Bins<K> gives up to the compiler's choice of instructions.
 constexpr int kAnyMaxK = 32;
 
 template <int KT>
@@ -96,21 +94,28 @@ __device__ __forceinline__ void build_knots(B bins, const float *u, float bound,
     float m = u[0];
 #pragma unroll B::unroll
     for (int k = 1; k < K; ++k) m = fmaxf(m, u[k]);
-    float s = 0.f;
+    // From the float exponentials on, the knots are built in double and rounded once (as the
+    // inference passes build theirs, flow_device.h).  In float, next to one logit far above the
+    // others the normaliser adds K - 1 equal small terms to ~1, each rounded the same way: at
+    // K = 32 every knot behind the wide bin was off by 42 ulp(B); and a cumulative sum rounded to
+    // float before the affine map leaves each knot 1 - 2 ulp(B) off, which a steep bin turns into
+    // 1e-3 of the log-det's gradients (tests/spline_sharp_cases.py).
+    double sd = 0.0;
 #pragma unroll B::unroll
     for (int k = 0; k < K; ++k) {
         kn.p[k] = expf(u[k] - m);
-        s += kn.p[k];
+        sd += (double)kn.p[k];
     }
-#pragma unroll B::unroll
-    for (int k = 0; k < K; ++k) kn.p[k] = kn.p[k] / s;
-    const float c1 = 1.f - kMin * (float)K;
+    const double inv = 1.0 / sd;
+    const double c1 = 1.0 - 1e-3 * (double)K;
     double cs = 0.0;
     kn.c[0] = -bound;
 #pragma unroll B::unroll
-    for (int k = 0; k < K - 1; ++k) {
-        cs += (double)(kMin + c1 * kn.p[k]);
-        kn.c[k + 1] = (2.f * bound) * (float)cs + (-bound);
+    for (int k = 0; k < K; ++k) {
+        const double pk = (double)kn.p[k] * inv;
+        kn.p[k] = (float)pk;
+        cs += 1e-3 + c1 * pk;
+        if (k < K - 1) kn.c[k + 1] = (float)((2.0 * (double)bound) * cs - (double)bound);
     }
     kn.c[K] = bound;
 }
@@ -172,7 +177,13 @@ __device__ __forceinline__ float rqs_bin_theta(float xv, float icw, float ibw, f
         const float c = -s * (xv - ich);
         const float disc = fabsf(bb * bb - 4.f * a * c);
         if (disc != disc && nan_flag) atomicOr(nan_flag, 1);
-        return (2.f * c) / (-bb - sqrtf(disc));
+        // The reference takes 2 c / (-bb - sqrt(disc)) whatever the sign of bb.  For bb < 0 that
+        // subtracts two nearly equal numbers; the same root as (-bb + sqrt(disc)) / (2 a) does not.
+        // The exact root lies in [0, 1]: pinned there, the logarithms of the log-det keep positive
+        // arguments where the discriminant itself cancels (flow_device.h, rqs_eval).  A NaN stays NaN.
+        const float sq = sqrtf(disc);
+        const float root = bb >= 0.f ? (2.f * c) / (-bb - sq) : (sq - bb) / (2.f * a);
+        return root > 1.f ? 1.f : (root < 0.f ? 0.f : root);
     }
     return (xv - icw) / ibw;
 }
@@ -324,48 +335,44 @@ __global__ __launch_bounds__(256) void rqs_forward_kernel(int64_t M, const float
 }
 
 // The knot adjoints of one element: only knots b and b + 1 of its bin carry one (gw0 / gw1 of the
-// width knots, gh0 / gh1 of the height knots).  With a compile-time K they are also spread over
-// dense register arrays g_c[0..K], which the instantiated kernels read; with a run-time K they stay
-// sparse.
+// width knots, gh0 / gh1 of the height knots).
 struct BinAdjoint {
     int b;
     float gw0, gw1, gh0, gh1;
 };
 
-// knot adjoints -> unnormalised-parameter adjoints; the knot adjoints are gc over c[0..K] with a
-// compile-time K, else g_b at knot b, g_b1 at knot b + 1 and zero elsewhere
+// knot adjoints (g_b at knot b, g_b1 at knot b + 1, zero elsewhere) -> unnormalised-parameter adjoints
 template <class B>
-__device__ __forceinline__ void knots_backward(B bins, const Knots<B> &kn, const float *gc, int b, float g_b,
-                                               float g_b1, float bound, float *gu) {
+__device__ __forceinline__ void knots_backward(B bins, const Knots<B> &kn, int b, float g_b, float g_b1, float bound,
+                                               float *gu) {
     const int K = bins.k();
     const float c1 = 1.f - kMin * (float)K;
-    // c[k] = 2B * C[k] - B (k = 1..K-1), C[k] = sum_{j<k} w_j; c[0], c[K] pinned
-    float gw[B::cap];
-    float suffix = 0.f;
+    // c[k] = 2B * C[k] - B (k = 1..K-1), C[k] = sum_{j<k} w_j; c[0], c[K] pinned.  The adjoint of w_j is
+    // v_j = Gb + Gb1 (j < b), Gb1 (j == b), 0 (j > b)
+    const float Gb = b >= 1 ? (2.f * bound) * g_b : 0.f;
+    const float Gb1 = b + 1 <= K - 1 ? (2.f * bound) * g_b1 : 0.f;
+    // softmax: gu_j = p_j c1 (v_j - sum_i p_i v_i).  Next to a p_i near 1 that difference cancels
+    // (1 % of the gradient at a logit 12 above the others).  With sum_i p_i = 1 it is
+    // sum_i p_i (v_j - v_i): over the three levels of v, sums of the p below, at and above bin b.
+    float plt = 0.f, pb = 0.f, pgt = 0.f;
 #pragma unroll B::unroll
-    for (int j = K - 1; j >= 0; --j) {
-        gw[j] = suffix;  // sum over k = j+1 .. K-1 of g_C[k]
-        float gcj;
-        if constexpr (B::fixed)
-            gcj = gc[j];
-        else
-            gcj = (j == b) ? g_b : ((j == b + 1) ? g_b1 : 0.f);
-        if (j >= 1) suffix += (2.f * bound) * gcj;  // add k = j for the next (smaller) j
+    for (int j = 0; j < K; ++j) {
+        plt += j < b ? kn.p[j] : 0.f;
+        pb = j == b ? kn.p[j] : pb;
+        pgt += j > b ? kn.p[j] : 0.f;
     }
-    float dot = 0.f;
+    const float below = Gb * pb + (Gb + Gb1) * pgt;      // j < b
+    const float at = Gb1 * pgt - Gb * plt;               // j == b
+    const float above = -((Gb + Gb1) * plt + Gb1 * pb);  // j > b
 #pragma unroll B::unroll
-    for (int j = 0; j < K; ++j) dot += kn.p[j] * (c1 * gw[j]);
-#pragma unroll B::unroll
-    for (int j = 0; j < K; ++j) gu[j] = kn.p[j] * (c1 * gw[j] - dot);
+    for (int j = 0; j < K; ++j) gu[j] = kn.p[j] * (c1 * (j < b ? below : (j == b ? at : above)));
 }
 
 // the adjoint core of one element inside [-B, B] from its built knots: gx, the bin's knot adjoints
-// (with a compile-time K also as gcw / gch over c[0..K]) and the derivative logits' adjoints
-// gud[0..K]
+// and the derivative logits' adjoints gud[0..K]
 template <bool INV, class B>
 __device__ __forceinline__ BinAdjoint rqs_bwd_core(B bins, float xv, const float *wc, const float *hc,
-                                                   const float *dd, float go, float gl, float &gx, float *gcw,
-                                                   float *gch, float *gud) {
+                                                   const float *dd, float go, float gl, float &gx, float *gud) {
     const int K = bins.k();
     const int b = find_bin(bins, xv, INV ? hc : wc);
     const float e0 = dd[b], e1 = dd[b + 1];
@@ -375,13 +382,6 @@ __device__ __forceinline__ BinAdjoint rqs_bwd_core(B bins, float xv, const float
     pick_bin<B>(hc, b, ich, ch1);
     const BinGrads r = rqs_bin_bwd<INV>(xv, icw, cw1, ich, ch1, d0, d1, go, gl);
     gx = r.gx;
-    if constexpr (B::fixed) {
-#pragma unroll
-        for (int k = 0; k <= K; ++k) {
-            gcw[k] = (k == b) ? (r.g_icw - r.g_ibw) : ((k == b + 1) ? r.g_ibw : 0.f);
-            gch[k] = (k == b) ? (r.g_ich - r.g_ih) : ((k == b + 1) ? r.g_ih : 0.f);
-        }
-    }
     FS_BINS_FOR(k, K + 1,
                 float g = 0.f;
                 if (k == b) g = r.g_d0 * softplus_grad(e0);
@@ -398,10 +398,9 @@ __device__ __forceinline__ void rqs_point_bwd(B bins, float xv, const float *uw,
     Knots<B> W, Hh;
     build_knots(bins, uw, bound, W);
     build_knots(bins, uh, bound, Hh);
-    float gcw[B::cap + 1], gch[B::cap + 1];
-    const BinAdjoint a = rqs_bwd_core<INV>(bins, xv, W.c, Hh.c, dd, go, gl, gx, gcw, gch, gud);
-    knots_backward(bins, W, gcw, a.b, a.gw0, a.gw1, bound, guw);
-    knots_backward(bins, Hh, gch, a.b, a.gh0, a.gh1, bound, guh);
+    const BinAdjoint a = rqs_bwd_core<INV>(bins, xv, W.c, Hh.c, dd, go, gl, gx, gud);
+    knots_backward(bins, W, a.b, a.gw0, a.gw1, bound, guw);
+    knots_backward(bins, Hh, a.b, a.gh0, a.gh1, bound, guh);
 }
 
 template <int KT, bool INV>
@@ -1032,17 +1031,13 @@ __device__ __forceinline__ void density_bwd_row4(B bins, const CouplingArgs &c, 
         float *guh = guw + c.n * K;
         float *gud = g_u + row * c.n * P + 2 * c.n * K + jj * (K + 1);
         // each wave stores its knot set's parameter adjoints and, on h == 0, gx and the derivative
-        // logits' adjoints.  The two policies read the knot adjoints differently (dense / sparse),
-        // and the stores keep the shape each had as a separate copy
+        // logits' adjoints.  The stores keep the shape each policy had as a separate copy
         if constexpr (B::fixed) {
             if (on && inside) {
-                float g, gcw[B::cap + 1], gch[B::cap + 1], gd[B::cap + 1];
+                float g, gd[B::cap + 1], gk[B::cap];
                 const BinAdjoint a = rqs_bwd_core<false>(bins, xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1),
-                                                         go, gl, g, gcw, gch, gd);
-                float gsel[B::cap + 1], gk[B::cap];
-#pragma unroll
-                for (int k = 0; k <= K; ++k) gsel[k] = h == 0 ? gcw[k] : gch[k];
-                knots_backward(bins, kn, gsel, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
+                                                         go, gl, g, gd);
+                knots_backward(bins, kn, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
                 if (part == 0) {
 #pragma unroll
                     for (int k = 0; k < K; ++k) gp[h * K + k] = gk[k] / c.sq;
@@ -1087,8 +1082,8 @@ __device__ __forceinline__ void density_bwd_row4(B bins, const CouplingArgs &c, 
             if (on && inside) {
                 float g, gd[B::cap + 1], gk[B::cap];
                 const BinAdjoint a = rqs_bwd_core<false>(bins, xv, wc, hc, part == 0 ? p + 2 * K : ud + jj * (K + 1),
-                                                         go, gl, g, nullptr, nullptr, gd);
-                knots_backward(bins, kn, nullptr, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
+                                                         go, gl, g, gd);
+                knots_backward(bins, kn, a.b, h == 0 ? a.gw0 : a.gh0, h == 0 ? a.gw1 : a.gh1, c.bound, gk);
                 for (int k = 0; k < K; ++k) gk_out[k] = part == 0 ? gk[k] / c.sq : gk[k];
                 if (h == 0) {
                     gx[row * c.D + pos] = g;

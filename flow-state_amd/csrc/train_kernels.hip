@@ -1179,21 +1179,36 @@ __global__ __launch_bounds__(kBnCols *kBnRg) void bn_relu_train_fwd_kernel(
     }
 }
 
+__device__ __forceinline__ double wg_colsum(double v, double (*red)[kBnCols], int c, int rg) {
+    red[rg][c] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < kBnRg; ++q) s += red[q][c];
+    __syncthreads();
+    return s;
+}
+
 // dz = dy * (y > 0); dbeta = sum dz; dgamma = sum dz xhat;
 // dx = gamma invstd (dz - dbeta / B - xhat dgamma / B)   (torch's batch_norm_backward_elemt)
+// The column sums are taken in double, and xhat is centred once more: the saved mean is a float
+// sum (the producer's tile statistics), off by ~1e-7 |x|, so xhat = (x - mean) invstd has a mean m of
+// its own, and sum dx = -B m dgamma / B does not vanish.  torch sums in double; with float sums and
+// no centring the bias gradient of a Linear in front of this BatchNorm, which is exactly zero,
+// came out 3 x torch's float32 rounding (tests/test_gpu_spline_sharp.py, the coupling layer).
 template <int R>
 __global__ __launch_bounds__(kBnCols *kBnRg) void bn_relu_train_bwd_kernel(
     int64_t B, int H, const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ dy,
     const float *__restrict__ gamma, const float *__restrict__ mean, const float *__restrict__ invstd,
     float *__restrict__ dx, const float *__restrict__ dx_add, float *__restrict__ dgamma, float *__restrict__ dbeta) {
-    __shared__ float red[kBnRg][kBnCols];
+    __shared__ double red[kBnRg][kBnCols];
     const int c = threadIdx.x % kBnCols, rg = threadIdx.x / kBnCols;
     const int col = blockIdx.x * kBnCols + c;
     const bool ok = col < H;
     const int64_t o = ok ? col : 0;
     const float mu = mean[o], is = invstd[o];
     float dzv[R > 0 ? R : 1], xhv[R > 0 ? R : 1];
-    float sd = 0.f, sdx = 0.f;
+    double sd = 0.0, sdx = 0.0, sx = 0.0;
     if (R > 0) {
 #pragma unroll
         for (int q = 0; q < R; ++q) {
@@ -1205,32 +1220,39 @@ __global__ __launch_bounds__(kBnCols *kBnRg) void bn_relu_train_bwd_kernel(
         }
 #pragma unroll
         for (int q = 0; q < R; ++q) {
-            sd += dzv[q];
-            sdx += dzv[q] * xhv[q];
+            sd += (double)dzv[q];
+            sdx += (double)(dzv[q] * xhv[q]);
+            sx += (double)xhv[q];
         }
     } else if (ok) {
         for (int64_t i = rg; i < B; i += kBnRg) {
             const float dz = y[i * H + o] > 0.f ? dy[i * H + o] : 0.f;
-            sd += dz;
-            sdx += dz * ((x[i * H + o] - mu) * is);
+            const float xh = (x[i * H + o] - mu) * is;
+            sd += (double)dz;
+            sdx += (double)(dz * xh);
+            sx += (double)xh;
         }
     }
-    const float db = wg_colsum(sd, red, c, rg);
-    const float dg = wg_colsum(sdx, red, c, rg);
+    const double dbd = wg_colsum(sd, red, c, rg);
+    const double dgr = wg_colsum(sdx, red, c, rg);
+    const double md = wg_colsum(sx, red, c, rg) / (double)B;  // xhat's own mean
     if (!ok) return;
+    const float m = (float)md;
+    const float db = (float)dbd, dg = (float)(dgr - md * dbd);  // sum dz (xhat - m)
     const float gm = gamma[col];
-    const float mdb = db / (float)B, mdg = dg / (float)B;
+    const float mdb = (float)(dbd / (double)B), mdg = (float)((dgr - md * dbd) / (double)B);
     if (R > 0) {
 #pragma unroll
         for (int q = 0; q < R; ++q) {
             const int64_t i = rg + (int64_t)q * kBnRg;
-            if (i < B) dx[i * H + col] = (dzv[q] - mdb - xhv[q] * mdg) * (is * gm) + (dx_add ? dx_add[i * H + col] : 0.f);
+            if (i < B)
+                dx[i * H + col] = (dzv[q] - mdb - (xhv[q] - m) * mdg) * (is * gm) + (dx_add ? dx_add[i * H + col] : 0.f);
         }
     } else {
         for (int64_t i = rg; i < B; i += kBnRg) {
             const float dz = y[i * H + col] > 0.f ? dy[i * H + col] : 0.f;
             const float xh = (x[i * H + col] - mu) * is;
-            dx[i * H + col] = (dz - mdb - xh * mdg) * (is * gm) + (dx_add ? dx_add[i * H + col] : 0.f);
+            dx[i * H + col] = (dz - mdb - (xh - m) * mdg) * (is * gm) + (dx_add ? dx_add[i * H + col] : 0.f);
         }
     }
     if (rg == 0) {

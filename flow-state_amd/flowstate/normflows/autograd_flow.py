@@ -44,6 +44,20 @@ def _knots(unnorm, min_size, lo, hi):
     return c, c[..., 1:] - c[..., :-1]
 
 
+class _PinnedRoot(torch.autograd.Function):
+    """The inverse root pinned to [0, 1] in value only: the device adjoint (rqs_bin_bwd)
+    differentiates the unpinned root at the pinned theta, so an element at y = +-B, whose float32
+    root passes 1 by an ulp, keeps its gradient."""
+
+    @staticmethod
+    def forward(ctx, root):
+        return root.clamp(0, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
 def rational_quadratic_spline(x, uw, uh, ud, inverse, left, right, bottom, top):
     """splines.py:91-222 (inputs already inside [left, right])."""
     cw, w = _knots(uw, MIN_BIN_WIDTH, left, right)
@@ -67,7 +81,15 @@ def rational_quadratic_spline(x, uw, uh, ud, inverse, left, right, bottom, top):
         c = -idl * (x - ich)
         disc = torch.abs(bb.pow(2) - 4 * a * c)
         _nan_flags.append(torch.isnan(disc).any())  # splines.py:176-183, raised after the pass
-        root = (2 * c) / (-bb - torch.sqrt(disc))
+        # The reference takes 2 c / (-bb - sqrt(disc)) whatever the sign of bb; for bb < 0 that
+        # cancels, the same root as (-bb + sqrt(disc)) / (2 a) does not.  Pinned to [0, 1], where
+        # the exact root lies (csrc/spline_autograd.hip rqs_bin_theta, flow_device.h rqs_eval).
+        sq = torch.sqrt(disc)
+        # (one division of the selected terms: a where over two quotients would send the unused
+        # quotient's 0 * inf into the gradients)
+        pos = bb >= 0
+        root = torch.where(pos, 2 * c, sq - bb) / torch.where(pos, -bb - sq, 2 * a)
+        root = _PinnedRoot.apply(root)
         out = root * ibw + icw
         tomt = root * (1 - root)
         den = idl + (id0 + id1 - 2 * idl) * tomt
