@@ -155,18 +155,58 @@ int fs_pcg64_random(uint64_t *state, int64_t C, double *out, void *stream) {
     return hip_rc(fs_pcg64_random_impl(state, C, out, (hipStream_t)stream), "fs_pcg64_random");
 }
 
+// fs_mh_accept / fs_mh_accept_beta (beta_c nullable: p->beta for every chain)
+static int mh_accept_checked(const char *who, const double *beta_c, const fs_phys *p, int64_t C, int32_t N,
+                             double *E_old, double *W_old, double *nll_old, const double *E_new, const double *W_new,
+                             const float *log_q_new, uint64_t *pcg, double *state, uint8_t *state_is_f32,
+                             const float *config, uint8_t *accept, int64_t *attempts, int64_t *accepted,
+                             unsigned long long *n_accept, int flags, void *stream) {
+    REQUIRE(p && C >= 0 && (C == 0 || (E_old && nll_old && E_new && log_q_new && pcg && accept)),
+            "%s: invalid arguments", who);
+    REQUIRE(N >= 1 && N <= fs::kMaxN, "%s: N=%d outside [1, %d]", who, N, fs::kMaxN);
+    REQUIRE((state == nullptr) == (config == nullptr), "%s: state and config go together", who);
+    return hip_rc(fs_mh_accept_impl(p, C, N, E_old, W_old, nll_old, E_new, W_new, log_q_new, pcg, state,
+                                    state_is_f32, config, accept, attempts, accepted, n_accept, flags,
+                                    (hipStream_t)stream, nullptr, nullptr, nullptr, beta_c),
+                  who);
+}
+
 int fs_mh_accept(const fs_phys *p, int64_t C, int32_t N, double *E_old, double *W_old, double *nll_old,
                  const double *E_new, const double *W_new, const float *log_q_new, uint64_t *pcg, double *state,
                  uint8_t *state_is_f32, const float *config, uint8_t *accept, int64_t *attempts, int64_t *accepted,
                  unsigned long long *n_accept, int flags, void *stream) {
-    REQUIRE(p && C >= 0 && (C == 0 || (E_old && nll_old && E_new && log_q_new && pcg && accept)),
-            "fs_mh_accept: invalid arguments");
-    REQUIRE(N >= 1 && N <= fs::kMaxN, "fs_mh_accept: N=%d outside [1, %d]", N, fs::kMaxN);
-    REQUIRE((state == nullptr) == (config == nullptr), "fs_mh_accept: state and config go together");
-    return hip_rc(fs_mh_accept_impl(p, C, N, E_old, W_old, nll_old, E_new, W_new, log_q_new, pcg, state,
-                                    state_is_f32, config, accept, attempts, accepted, n_accept, flags,
-                                    (hipStream_t)stream),
-                  "fs_mh_accept");
+    return mh_accept_checked("fs_mh_accept", nullptr, p, C, N, E_old, W_old, nll_old, E_new, W_new, log_q_new, pcg,
+                             state, state_is_f32, config, accept, attempts, accepted, n_accept, flags, stream);
+}
+
+int fs_mh_accept_beta(const double *beta_c, const fs_phys *p, int64_t C, int32_t N, double *E_old, double *W_old,
+                      double *nll_old, const double *E_new, const double *W_new, const float *log_q_new,
+                      uint64_t *pcg, double *state, uint8_t *state_is_f32, const float *config, uint8_t *accept,
+                      int64_t *attempts, int64_t *accepted, unsigned long long *n_accept, int flags, void *stream) {
+    return mh_accept_checked("fs_mh_accept_beta", beta_c, p, C, N, E_old, W_old, nll_old, E_new, W_new, log_q_new,
+                             pcg, state, state_is_f32, config, accept, attempts, accepted, n_accept, flags, stream);
+}
+
+int fs_replica_exchange(int64_t R, int32_t T, int32_t N, int32_t parity, const double *beta_c, double *state,
+                        uint8_t *state_is_f32, double *E, double *W, double *nll, uint64_t *pcg,
+                        int32_t *replica_id, int64_t *swap_attempts, int64_t *swap_accepts, int8_t *trip_dir,
+                        int64_t *round_trips, void *stream) {
+    REQUIRE(R >= 0 && R <= (int64_t)1 << 40, "fs_replica_exchange: R=%lld outside [0, 2^40]", (long long)R);
+    REQUIRE(T >= 2 && T <= 1 << 20, "fs_replica_exchange: T=%d, a ladder has 2 to 2^20 rungs", T);
+    REQUIRE(R * (T / 2) < (int64_t)4 << 30, "fs_replica_exchange: R=%lld x T=%d pairs exceed one launch",
+            (long long)R, T);
+    REQUIRE(parity == 0 || parity == 1, "fs_replica_exchange: parity=%d is not 0 or 1", parity);
+    REQUIRE(N >= 1 && N <= fs::kMaxN, "fs_replica_exchange: N=%d outside [1, %d]", N, fs::kMaxN);
+    REQUIRE(R == 0 || beta_c, "fs_replica_exchange: beta_c is NULL");
+    REQUIRE(R == 0 || state, "fs_replica_exchange: state is NULL");
+    REQUIRE(((uintptr_t)state & 15) == 0, "fs_replica_exchange: state must be 16-byte aligned");
+    REQUIRE(R == 0 || E, "fs_replica_exchange: E is NULL");
+    REQUIRE(R == 0 || pcg, "fs_replica_exchange: pcg is NULL");
+    REQUIRE(!(trip_dir || round_trips) || (replica_id && trip_dir),
+            "fs_replica_exchange: round_trips needs trip_dir, and trip_dir needs replica_id");
+    return hip_rc(fs_replica_exchange_impl(R, T, N, parity, beta_c, state, state_is_f32, E, W, nll, pcg, replica_id,
+                                           swap_attempts, swap_accepts, trip_dir, round_trips, (hipStream_t)stream),
+                  "fs_replica_exchange");
 }
 
 int fs_min_image(const fs_phys *p, const void *pos1, int64_t stride1, const void *pos2, int pos_is_f32, int64_t n,
@@ -201,14 +241,17 @@ int64_t fs_nf_mh_step_ws_bytes(const fs_flow_dims *d, int64_t C) {
     return fs::rup(C * D * 4, 256) + fs::rup(2 * C * D * 4, 256) + fs::rup(2 * C * 4, 256) + fs::rup(C * 8, 256) * 4;
 }
 
-int fs_nf_mh_step(const fs_flow_dims *d, const void *packed, const fs_phys *p, int64_t C, uint64_t seed,
-                  uint64_t step, int64_t chain_offset, double *E_old, double *W_old, double *nll_old, uint64_t *pcg, double *state,
-                  uint8_t *state_is_f32, uint8_t *accept, int64_t *attempts, int64_t *accepted,
-                  unsigned long long *n_accept, int32_t *err, int flags, void *ws, void *stream) {
+// fs_nf_mh_step / fs_nf_mh_step_beta (beta_c nullable: p->beta for every chain; only the
+// accept reads it).  The stage names in HIP error messages are fs_nf_mh_step's for both.
+static int nf_mh_step_checked(const char *who, const double *beta_c, const fs_flow_dims *d, const void *packed,
+                              const fs_phys *p, int64_t C, uint64_t seed, uint64_t step, int64_t chain_offset,
+                              double *E_old, double *W_old, double *nll_old, uint64_t *pcg, double *state,
+                              uint8_t *state_is_f32, uint8_t *accept, int64_t *attempts, int64_t *accepted,
+                              unsigned long long *n_accept, int32_t *err, int flags, void *ws, void *stream) {
     int rc = check_dims(d);
     if (rc) return rc;
-    REQUIRE(p && C >= 0 && (C == 0 || (packed && E_old && nll_old && pcg && accept && ws)), "fs_nf_mh_step: invalid arguments");
-    REQUIRE(((uintptr_t)ws & 255) == 0, "fs_nf_mh_step: workspace must be 256-byte aligned");
+    REQUIRE(p && C >= 0 && (C == 0 || (packed && E_old && nll_old && pcg && accept && ws)), "%s: invalid arguments", who);
+    REQUIRE(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", who);
     if (C == 0) return FS_OK;
     const int64_t D = 2 * d->N;
     char *w = (char *)ws;
@@ -231,7 +274,7 @@ int fs_nf_mh_step(const fs_flow_dims *d, const void *packed, const fs_phys *p, i
     const double half_width = p->Lx / 2.0;  // MonteCarlo.half_width (monte_carlo.py:66)
     const bool hybrid = (flags & FS_MH_HYBRID) != 0;
     const bool single = (flags & FS_MH_SINGLE_PASS) != 0;
-    REQUIRE(!hybrid || state, "fs_nf_mh_step: FS_MH_HYBRID needs the state");
+    REQUIRE(!hybrid || state, "%s: FS_MH_HYBRID needs the state", who);
     hipError_t e = fs_flow_pass_impl(d, packed, 2, nullptr, C, nullptr, single ? log_q : nullptr, single ? 1 : 0,
                                      config, centered, seed, step, chain_offset, half_width, err, st);
     if (e != hipSuccess) return hip_rc(e, "fs_nf_mh_step/propose");
@@ -257,8 +300,27 @@ int fs_nf_mh_step(const fs_flow_dims *d, const void *packed, const fs_phys *p, i
     }
     e = fs_mh_accept_impl(p, C, d->N, E_old, W_old, nll_old, E_new, W_new, log_q, pcg, state, state_is_f32,
                           state ? config : nullptr, accept, attempts, accepted, n_accept, flags, st,
-                          hybrid ? log_q_old : nullptr, hybrid ? E_cur : nullptr, hybrid ? W_cur : nullptr);
+                          hybrid ? log_q_old : nullptr, hybrid ? E_cur : nullptr, hybrid ? W_cur : nullptr, beta_c);
     return hip_rc(e, "fs_nf_mh_step/accept");
+}
+
+int fs_nf_mh_step(const fs_flow_dims *d, const void *packed, const fs_phys *p, int64_t C, uint64_t seed,
+                  uint64_t step, int64_t chain_offset, double *E_old, double *W_old, double *nll_old, uint64_t *pcg, double *state,
+                  uint8_t *state_is_f32, uint8_t *accept, int64_t *attempts, int64_t *accepted,
+                  unsigned long long *n_accept, int32_t *err, int flags, void *ws, void *stream) {
+    return nf_mh_step_checked("fs_nf_mh_step", nullptr, d, packed, p, C, seed, step, chain_offset, E_old, W_old,
+                              nll_old, pcg, state, state_is_f32, accept, attempts, accepted, n_accept, err, flags, ws,
+                              stream);
+}
+
+int fs_nf_mh_step_beta(const double *beta_c, const fs_flow_dims *d, const void *packed, const fs_phys *p, int64_t C,
+                       uint64_t seed, uint64_t step, int64_t chain_offset, double *E_old, double *W_old,
+                       double *nll_old, uint64_t *pcg, double *state, uint8_t *state_is_f32, uint8_t *accept,
+                       int64_t *attempts, int64_t *accepted, unsigned long long *n_accept, int32_t *err, int flags,
+                       void *ws, void *stream) {
+    return nf_mh_step_checked("fs_nf_mh_step_beta", beta_c, d, packed, p, C, seed, step, chain_offset, E_old, W_old,
+                              nll_old, pcg, state, state_is_f32, accept, attempts, accepted, n_accept, err, flags, ws,
+                              stream);
 }
 
 int64_t fs_nf_mh_steps_ws_bytes(const fs_flow_dims *d, int64_t C, int64_t S) {
@@ -391,23 +453,47 @@ int fs_nf_mh_step_banked(const fs_flow_dims *d, const void *packed, const fs_phy
     return hip_rc(e, "fs_nf_mh_step_banked/accept");
 }
 
+// fs_local_moves / fs_local_moves_if / fs_local_moves_beta (gate, beta_c nullable)
+static int local_moves_checked(const char *who, const double *beta_c, const uint8_t *gate, const fs_phys *p, int64_t C,
+                               int32_t N, double *state, const uint8_t *state_is_f32, double *E, double *W,
+                               uint64_t *pcg, uint64_t *pcg_buf, double *max_disp, int64_t *attempts,
+                               int64_t *accepted, int64_t *prev_counts, int64_t n_moves, int64_t step0,
+                               int32_t adjust_every, double target_acceptance, int32_t sample_every,
+                               double *samples_xy, double *samples_ew, uint8_t *accept_log,
+                               unsigned long long *n_accept, void *stream) {
+    REQUIRE(p && C >= 0 && n_moves >= 0 && step0 >= 0 &&
+                (C == 0 || (state && E && pcg && pcg_buf && max_disp && attempts && accepted)),
+            "%s: invalid arguments", who);
+    REQUIRE(N >= 1 && N <= fs::kMaxN, "%s: N=%d outside [1, %d]", who, N, fs::kMaxN);
+    REQUIRE(adjust_every <= 0 || (prev_counts && target_acceptance > 0.0),
+            "%s: adjust_every needs prev_counts and target_acceptance > 0", who);
+    REQUIRE(fs_local_samples_per_chain(step0, n_moves, sample_every) == 0 || samples_xy || samples_ew,
+            "%s: sample_every needs a sample buffer", who);
+    return hip_rc(fs_local_moves_impl(p, C, N, state, state_is_f32, E, W, pcg, pcg_buf, max_disp, attempts, accepted,
+                                      prev_counts, n_moves, step0, adjust_every, target_acceptance, sample_every,
+                                      samples_xy, samples_ew, accept_log, n_accept, (hipStream_t)stream, gate, beta_c),
+                  who);
+}
+
 int fs_local_moves(const fs_phys *p, int64_t C, int32_t N, double *state, const uint8_t *state_is_f32, double *E,
                    double *W, uint64_t *pcg, uint64_t *pcg_buf, double *max_disp, int64_t *attempts,
                    int64_t *accepted, int64_t *prev_counts, int64_t n_moves, int64_t step0, int32_t adjust_every,
                    double target_acceptance, int32_t sample_every, double *samples_xy, double *samples_ew,
                    uint8_t *accept_log, unsigned long long *n_accept, void *stream) {
-    REQUIRE(p && C >= 0 && n_moves >= 0 && step0 >= 0 &&
-                (C == 0 || (state && E && pcg && pcg_buf && max_disp && attempts && accepted)),
-            "fs_local_moves: invalid arguments");
-    REQUIRE(N >= 1 && N <= fs::kMaxN, "fs_local_moves: N=%d outside [1, %d]", N, fs::kMaxN);
-    REQUIRE(adjust_every <= 0 || (prev_counts && target_acceptance > 0.0),
-            "fs_local_moves: adjust_every needs prev_counts and target_acceptance > 0");
-    REQUIRE(fs_local_samples_per_chain(step0, n_moves, sample_every) == 0 || samples_xy || samples_ew,
-            "fs_local_moves: sample_every needs a sample buffer");
-    return hip_rc(fs_local_moves_impl(p, C, N, state, state_is_f32, E, W, pcg, pcg_buf, max_disp, attempts, accepted,
-                                      prev_counts, n_moves, step0, adjust_every, target_acceptance, sample_every,
-                                      samples_xy, samples_ew, accept_log, n_accept, (hipStream_t)stream),
-                  "fs_local_moves");
+    return local_moves_checked("fs_local_moves", nullptr, nullptr, p, C, N, state, state_is_f32, E, W, pcg, pcg_buf,
+                               max_disp, attempts, accepted, prev_counts, n_moves, step0, adjust_every,
+                               target_acceptance, sample_every, samples_xy, samples_ew, accept_log, n_accept, stream);
+}
+
+int fs_local_moves_beta(const double *beta_c, const fs_phys *p, int64_t C, int32_t N, double *state,
+                        const uint8_t *state_is_f32, double *E, double *W, uint64_t *pcg, uint64_t *pcg_buf,
+                        double *max_disp, int64_t *attempts, int64_t *accepted, int64_t *prev_counts,
+                        int64_t n_moves, int64_t step0, int32_t adjust_every, double target_acceptance,
+                        int32_t sample_every, double *samples_xy, double *samples_ew, uint8_t *accept_log,
+                        unsigned long long *n_accept, const uint8_t *gate, void *stream) {
+    return local_moves_checked("fs_local_moves_beta", beta_c, gate, p, C, N, state, state_is_f32, E, W, pcg, pcg_buf,
+                               max_disp, attempts, accepted, prev_counts, n_moves, step0, adjust_every,
+                               target_acceptance, sample_every, samples_xy, samples_ew, accept_log, n_accept, stream);
 }
 
 int fs_local_moves_if(const uint8_t *gate, const fs_phys *p, int64_t C, int32_t N, double *state,
@@ -417,18 +503,9 @@ int fs_local_moves_if(const uint8_t *gate, const fs_phys *p, int64_t C, int32_t 
                       int32_t sample_every, double *samples_xy, double *samples_ew, uint8_t *accept_log,
                       unsigned long long *n_accept, void *stream) {
     REQUIRE(gate, "fs_local_moves_if: gate is required");
-    REQUIRE(p && C >= 0 && n_moves >= 0 && step0 >= 0 &&
-                (C == 0 || (state && E && pcg && pcg_buf && max_disp && attempts && accepted)),
-            "fs_local_moves_if: invalid arguments");
-    REQUIRE(N >= 1 && N <= fs::kMaxN, "fs_local_moves_if: N=%d outside [1, %d]", N, fs::kMaxN);
-    REQUIRE(adjust_every <= 0 || (prev_counts && target_acceptance > 0.0),
-            "fs_local_moves_if: adjust_every needs prev_counts and target_acceptance > 0");
-    REQUIRE(fs_local_samples_per_chain(step0, n_moves, sample_every) == 0 || samples_xy || samples_ew,
-            "fs_local_moves_if: sample_every needs a sample buffer");
-    return hip_rc(fs_local_moves_impl(p, C, N, state, state_is_f32, E, W, pcg, pcg_buf, max_disp, attempts, accepted,
-                                      prev_counts, n_moves, step0, adjust_every, target_acceptance, sample_every,
-                                      samples_xy, samples_ew, accept_log, n_accept, (hipStream_t)stream, gate),
-                  "fs_local_moves_if");
+    return local_moves_checked("fs_local_moves_if", nullptr, gate, p, C, N, state, state_is_f32, E, W, pcg, pcg_buf,
+                               max_disp, attempts, accepted, prev_counts, n_moves, step0, adjust_every,
+                               target_acceptance, sample_every, samples_xy, samples_ew, accept_log, n_accept, stream);
 }
 
 int fs_chains_copy_if(const uint8_t *gate, int64_t C, int32_t N, const fs_local_chains *src,

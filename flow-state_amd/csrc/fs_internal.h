@@ -45,7 +45,12 @@ hipError_t fs_mh_accept_impl(const fs_phys *p, int64_t C, int N, double *E_old, 
                              double *state, uint8_t *state_is_f32, const float *config, uint8_t *accept,
                              int64_t *attempts, int64_t *accepted, unsigned long long *n_accept, int flags,
                              hipStream_t st, const float *log_q_old = nullptr, const double *E_cur = nullptr,
-                             const double *W_cur = nullptr);
+                             const double *W_cur = nullptr, const double *beta_c = nullptr);
+// one replica-exchange round of a temperature ladder (physics_kernels.hip)
+hipError_t fs_replica_exchange_impl(int64_t R, int T, int N, int parity, const double *beta_c, double *state,
+                                    uint8_t *state_is_f32, double *E, double *W, double *nll, uint64_t *pcg,
+                                    int32_t *replica_id, int64_t *swap_attempts, int64_t *swap_accepts,
+                                    int8_t *trip_dir, int64_t *round_trips, hipStream_t st);
 hipError_t fs_min_image_impl(const fs_phys *p, const void *a, int64_t sa, const void *b, int f32, int64_t n,
                             double *delta, double *r, hipStream_t st);
 hipError_t fs_particle_energy_impl(const fs_phys *p, const void *pos, int f32, int64_t C, int N, const int32_t *part,
@@ -112,7 +117,7 @@ hipError_t fs_local_moves_impl(const fs_phys *p, int64_t C, int N, double *state
                                int64_t *attempts, int64_t *accepted, int64_t *prev, int64_t n_moves, int64_t step0,
                                int adjust_every, double target, int sample_every, double *samples_xy,
                                double *samples_ew, uint8_t *accept_log, unsigned long long *n_accept,
-                               hipStream_t st, const uint8_t *gate = nullptr);
+                               hipStream_t st, const uint8_t *gate = nullptr, const double *beta_c = nullptr);
 hipError_t fs_chains_copy_if_impl(const uint8_t *gate, int64_t C, int N, const fs_local_chains *src,
                                   const fs_local_chains *dst, hipStream_t st);
 

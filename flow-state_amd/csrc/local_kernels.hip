@@ -51,6 +51,7 @@ struct LocalArgs {
     unsigned long long *n_accept;
     PairThresh T;  // squared-distance / min-image thresholds (physics_device.h)
     const uint8_t *gate;  // nullable: the launch does nothing when *gate == 0
+    const double *beta_c;  // [C] per-chain inverse temperature, read by the PCB kernels only
 };
 
 constexpr int kLocalWaves = 4;
@@ -173,7 +174,10 @@ __device__ __forceinline__ int nth_set_bit(uint64_t m, int k) {
 // boundary on, so no wave runs both dtypes' branches (a chain's state turns float32 after an
 // accepted big move, monte_carlo.py:289-292; a wave holding both ran each move's position and
 // distance code twice).  Each chain still runs the same code on its own lanes: the same bits.
-template <int LPC, int PPL, bool SORT = false>
+// PCB (a temperature ladder, fs_local_moves_beta): the accept reads the chain's own
+// beta_c[c] instead of p.beta; nothing else differs, so a chain runs bit for bit as in a
+// uniform launch at that beta, and the uniform instantiation is the kernel without it.
+template <int LPC, int PPL, bool SORT = false, bool PCB = false>
 __global__ void __launch_bounds__(64 * kLocalWaves * (SORT ? 2 : 1), LPC == 64 ? 4 : 2)
     local_moves_kernel(LocalArgs a) {
     constexpr int G = 64 / LPC;          // chains per wave
@@ -220,6 +224,9 @@ __global__ void __launch_bounds__(64 * kLocalWaves * (SORT ? 2 : 1), LPC == 64 ?
     rng.has = (uint32_t)uniform_u64<LPC>(a.pcg_buf[2 * c]);
     rng.buf = (uint32_t)uniform_u64<LPC>(a.pcg_buf[2 * c + 1]);
     double E = a.E[c], W = a.W ? a.W[c] : 0.0, md = a.max_disp[c];
+    [[maybe_unused]] double beta_own = 0.0;  // (PCB) this chain's beta, group-uniform
+    if constexpr (PCB)
+        beta_own = __longlong_as_double((long long)uniform_u64<LPC>((uint64_t)__double_as_longlong(a.beta_c[c])));
     int64_t att = a.attempts[c], acc_n = a.accepted[c];
     int64_t prev_att = a.prev ? a.prev[2 * c] : 0, prev_acc = a.prev ? a.prev[2 * c + 1] : 0;
     const double sr6c = pow6(1.0 / P.r_cut);
@@ -374,6 +381,7 @@ __global__ void __launch_bounds__(64 * kLocalWaves * (SORT ? 2 : 1), LPC == 64 ?
         bool accept;
         if (enn <= eno) accept = true;
         else if (isinf(enn)) accept = false;
+        else if constexpr (PCB) accept = pcg64_double(rng) < exp(-beta_own * (enn - eno));
         else accept = pcg64_double(rng) < exp(-P.beta * (enn - eno));
         if (accept) {
             acc_n += 1;
@@ -468,12 +476,12 @@ hipError_t fs_local_moves_impl(const fs_phys *p, int64_t C, int N, double *state
                                int64_t *attempts, int64_t *accepted, int64_t *prev, int64_t n_moves, int64_t step0,
                                int adjust_every, double target, int sample_every, double *samples_xy,
                                double *samples_ew, uint8_t *accept_log, unsigned long long *n_accept,
-                               hipStream_t st, const uint8_t *gate) {
+                               hipStream_t st, const uint8_t *gate, const double *beta_c) {
     if (C <= 0 || n_moves <= 0) return hipSuccess;
     LocalArgs a{*p,       C,         N,        state,      is_f32,     E,          W,
                 pcg,      pcg_buf,   max_disp, attempts,   accepted,   prev,       n_moves,
                 step0,    adjust_every, target, sample_every, fs_local_samples_per_chain(step0, n_moves, sample_every),
-                samples_xy, samples_ew, accept_log, n_accept, fs_pair_thresh(*p), gate};
+                samples_xy, samples_ew, accept_log, n_accept, fs_pair_thresh(*p), gate, beta_c};
     // lanes per chain x particles per lane (FS_LOCAL_LAYOUT=LPCxPPL overrides, for A/B runs).
     // Measured at 65536 chains x 1000 moves (sparse in-cutoff sums): N=64 8x8 2.41 G moves/s
     // (16x4 1.88 G, 64x1 1.06 G, 4x16 1.69 G: register-limited); N=32 4x8 4.04 G (8x4 3.20 G);
@@ -520,18 +528,23 @@ hipError_t fs_local_moves_impl(const fs_phys *p, int64_t C, int N, double *state
         return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
     }();
     const bool excl = excl_env == 1 || (excl_env < 0 && grid.x <= 8);
-#define FS_LLAUNCH(L, Q, S)                                                                       \
+#define FS_LLAUNCH_B(L, Q, S, B)                                                                  \
     {                                                                                             \
         unsigned dyn = 0;                                                                         \
         if (excl) {                                                                               \
             dyn = 131072u - (unsigned)sizeof(double) * kLocalWaves * (S ? 2 : 1) * 4 * 64 * Q;    \
-            if (hipError_t e = local_dyn_lds_once((const void *)local_moves_kernel<L, Q, S>, dyn); \
+            if (hipError_t e = local_dyn_lds_once((const void *)local_moves_kernel<L, Q, S, B>, dyn); \
                 e != hipSuccess)                                                                  \
                 return e;                                                                         \
         }                                                                                         \
-        hipLaunchKernelGGL((local_moves_kernel<L, Q, S>), grid, dim3(64 * kLocalWaves * (S ? 2 : 1)), dyn, st, \
+        hipLaunchKernelGGL((local_moves_kernel<L, Q, S, B>), grid, dim3(64 * kLocalWaves * (S ? 2 : 1)), dyn, st, \
                            a);                                                                    \
         return hipGetLastError();                                                                 \
+    }
+#define FS_LLAUNCH(L, Q, S)                   \
+    {                                         \
+        if (beta_c) FS_LLAUNCH_B(L, Q, S, true) \
+        FS_LLAUNCH_B(L, Q, S, false)          \
     }
 #define FS_LCASE(L, Q) \
     if (lpc == L && ppl == Q) FS_LLAUNCH(L, Q, false)
@@ -545,6 +558,7 @@ hipError_t fs_local_moves_impl(const fs_phys *p, int64_t C, int N, double *state
 #undef FS_LCASE_S
 #undef FS_LCASE
 #undef FS_LLAUNCH
+#undef FS_LLAUNCH_B
     return hipErrorInvalidValue;
 }
 

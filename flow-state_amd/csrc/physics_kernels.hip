@@ -272,19 +272,20 @@ __global__ void __launch_bounds__(256) mh_accept_kernel(fs_phys p, int64_t C, in
                                                         uint8_t *accept, int64_t *attempts, int64_t *accepted,
                                                         unsigned long long *n_accept, int flags,
                                                         const float *log_q_old, const double *E_cur,
-                                                        const double *W_cur) {
+                                                        const double *W_cur, const double *beta_c) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool valid = c < C;
     int acc = 0;
     if (valid) {
+        const double beta = beta_c ? beta_c[c] : p.beta;  // a temperature ladder: the chain's own (fs_mh_accept_beta)
         const double en = E_new[c];
         const double nll_new = -(double)log_q_new[c];  // - log_prob(new).item()
         const double dE = en - E_old[c];
         // hybrid: old NLL of the current (locally moved) state, monte_carlo.py:251-261
         const double no = log_q_old ? -(double)log_q_old[c] : nll_old[c];
         const double dN = nll_new - no;
-        const double ratio_log = (flags & FS_MH_CORRECT_SIGN) ? (-p.beta * dE + dN) : (-p.beta * dE - dN);
+        const double ratio_log = (flags & FS_MH_CORRECT_SIGN) ? (-beta * dE + dN) : (-beta * dE - dN);
         const double ratio = exp(ratio_log);
         if (ratio >= 1.0) {
             acc = 1;
@@ -318,6 +319,94 @@ __global__ void __launch_bounds__(256) mh_accept_kernel(fs_phys p, int64_t C, in
             m &= m - 1;
             const int64_t cc = base + b;
             for (int t = lane; t < D; t += 64) state[cc * D + t] = (double)config[cc * D + t];
+        }
+    }
+}
+
+// ---------------------------------------------------------------- replica exchange
+// One round of parallel tempering over R ladders of T rungs (chain r T + t = rung t of
+// ladder r, beta_c ascending in temperature; not in the reference).  Parity s pairs rungs
+// (t, t + 1) for t = s, s + 2, ... < T - 1: the pairs of a round are disjoint, so one wave
+// owns one pair and no wave waits for another.  Lane 0 decides in double:
+//   E_i or E_j not finite: reject, no draw;
+//   d = (beta_i - beta_j) (E_i - E_j);  d >= 0: accept, no draw (the big move's ratio >= 1);
+//   else accept iff Generator.random() < exp(d) on chain i's PCG64 stream.
+// A chain index is a temperature, so an accepted exchange moves the configurations: the
+// state rows (all 64 lanes, 16-byte loads and stores over the two adjacent rows), the dtype
+// flag, E, W, nll and the configuration's label replica_id; pcg and everything the local
+// moves tune per temperature stay.  trip_dir / round_trips follow each label (index
+// r T + label): 1 after rung 0, 2 after rung T - 1 when it came from rung 0; a return to rung
+// 0 with 2 completes a round trip.  No LDS, atomics or allocation.
+constexpr int kExchangeWaves = 4;
+__global__ void __launch_bounds__(64 * kExchangeWaves)
+    replica_exchange_kernel(int64_t n_pairs, int pairs_per_ladder, int T, int N, int parity,
+                            const double *__restrict__ beta_c, double *__restrict__ state,
+                            uint8_t *__restrict__ state_is_f32, double *__restrict__ E, double *__restrict__ W,
+                            double *__restrict__ nll, uint64_t *__restrict__ pcg, int32_t *__restrict__ replica_id,
+                            int64_t *__restrict__ swap_attempts, int64_t *__restrict__ swap_accepts,
+                            int8_t *__restrict__ trip_dir, int64_t *__restrict__ round_trips) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * kExchangeWaves + (threadIdx.x >> 6);
+    if (w >= n_pairs) return;  // whole waves leave
+    const int64_t r = w / pairs_per_ladder;
+    const int t = parity + 2 * (int)(w % pairs_per_ladder);
+    const int64_t i = r * T + t, j = i + 1;
+    int acc = 0;
+    if (lane == 0) {
+        const double ei = E[i], ej = E[j];
+        if (isfinite(ei) && isfinite(ej)) {
+            const double d = (beta_c[i] - beta_c[j]) * (ei - ej);
+            if (d >= 0.0) acc = 1;
+            else acc = pcg64_next_double(pcg + 4 * i) < exp(d) ? 1 : 0;
+        }
+    }
+    acc = __builtin_amdgcn_readlane(acc, 0);
+    if (acc) {
+        // rows i and j are adjacent: N double2 each (the state is 16-byte aligned, N <= 64)
+        double2 *rows = reinterpret_cast<double2 *>(state) + i * N;
+        if (lane < N) {
+            const double2 a = rows[lane], b = rows[N + lane];
+            rows[lane] = b;
+            rows[N + lane] = a;
+        }
+    }
+    if (lane != 0) return;
+    if (acc) {
+        const double ei = E[i];
+        E[i] = E[j];
+        E[j] = ei;
+        if (W) {
+            const double wi = W[i];
+            W[i] = W[j];
+            W[j] = wi;
+        }
+        if (nll) {
+            const double ni = nll[i];
+            nll[i] = nll[j];
+            nll[j] = ni;
+        }
+        if (state_is_f32) {
+            const uint8_t fi = state_is_f32[i];
+            state_is_f32[i] = state_is_f32[j];
+            state_is_f32[j] = fi;
+        }
+        if (replica_id) {
+            const int32_t li = replica_id[i];
+            replica_id[i] = replica_id[j];
+            replica_id[j] = li;
+        }
+    }
+    if (swap_attempts) swap_attempts[i] += 1;
+    if (swap_accepts && acc) swap_accepts[i] += 1;
+    if (replica_id && trip_dir) {
+        if (t == 0) {  // the label now at rung 0
+            const int64_t k = r * T + replica_id[i];
+            if (trip_dir[k] == 2 && round_trips) round_trips[k] += 1;
+            trip_dir[k] = 1;
+        }
+        if (t + 1 == T - 1) {  // the label now at the top rung
+            const int64_t k = r * T + replica_id[j];
+            if (trip_dir[k] == 1) trip_dir[k] = 2;
         }
     }
 }
@@ -550,11 +639,25 @@ hipError_t fs_mh_accept_impl(const fs_phys *p, int64_t C, int N, double *E_old, 
                              const double *E_new, const double *W_new, const float *log_q_new, uint64_t *pcg,
                              double *state, uint8_t *state_is_f32, const float *config, uint8_t *accept,
                              int64_t *attempts, int64_t *accepted, unsigned long long *n_accept, int flags,
-                             hipStream_t st, const float *log_q_old, const double *E_cur, const double *W_cur) {
+                             hipStream_t st, const float *log_q_old, const double *E_cur, const double *W_cur,
+                             const double *beta_c) {
     if (C <= 0) return hipSuccess;
     hipLaunchKernelGGL(mh_accept_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, *p, C, N, E_old,
                        W_old, nll_old, E_new, W_new, log_q_new, pcg, state, state_is_f32, config, accept,
-                       attempts, accepted, n_accept, flags, log_q_old, E_cur, W_cur);
+                       attempts, accepted, n_accept, flags, log_q_old, E_cur, W_cur, beta_c);
+    return hipGetLastError();
+}
+
+hipError_t fs_replica_exchange_impl(int64_t R, int T, int N, int parity, const double *beta_c, double *state,
+                                    uint8_t *state_is_f32, double *E, double *W, double *nll, uint64_t *pcg,
+                                    int32_t *replica_id, int64_t *swap_attempts, int64_t *swap_accepts,
+                                    int8_t *trip_dir, int64_t *round_trips, hipStream_t st) {
+    const int ppl = (T - parity) / 2;  // rungs parity, parity + 2, ... below T - 1
+    const int64_t n_pairs = R * ppl;
+    if (n_pairs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(replica_exchange_kernel, dim3((unsigned)((n_pairs + kExchangeWaves - 1) / kExchangeWaves)),
+                       dim3(64 * kExchangeWaves), 0, st, n_pairs, ppl, T, N, parity, beta_c, state, state_is_f32, E, W,
+                       nll, pcg, replica_id, swap_attempts, swap_accepts, trip_dir, round_trips);
     return hipGetLastError();
 }
 

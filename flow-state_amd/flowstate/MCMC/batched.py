@@ -233,14 +233,8 @@ class BatchedMonteCarlo:
                 continue
             S = 1 if self._moved else min(n - done, fill)
             if S == 1:
-                _lib.check(L.fs_nf_mh_step(dims, _lib.ptr(packed), self.phys.c, self.C, self.proposal_seed,
-                                           self.step_count, self.chain_offset, _lib.ptr(self.E_old),
-                                           _lib.ptr(self.W_old), _lib.ptr(self.nll_old), _lib.ptr(self.pcg),
-                                           _lib.ptr(self.state), _lib.ptr(self.state_is_f32), _lib.ptr(self.accept),
-                                           _lib.ptr(self.attempts), _lib.ptr(self.accepted), _lib.ptr(self.n_accept),
-                                           _lib.ptr(self.err), self.flags | (_lib.FS_MH_HYBRID if self._moved else 0)
-                                           | (_lib.FS_MH_SINGLE_PASS if self.single_pass_log_q else 0),
-                                           _lib.ptr(self._workspace()), st), "fs_nf_mh_step")
+                self._launch_fused_step(L, dims, packed, self.flags | (_lib.FS_MH_HYBRID if self._moved else 0)
+                                        | (_lib.FS_MH_SINGLE_PASS if self.single_pass_log_q else 0), st)
                 self._last_src = (self._ws, self.C, 0)
             else:
                 _lib.check(L.fs_nf_mh_steps(dims, _lib.ptr(packed), self.phys.c, self.C, S, self.proposal_seed,
@@ -256,6 +250,15 @@ class BatchedMonteCarlo:
             self._moved = False
         self._last_packed = weakref.ref(packed)  # not kept alive past a repack
         return self.accept
+
+    def _launch_fused_step(self, L, dims, packed, flags, st):
+        """One fused step of step() (a temperature-ladder engine launches its own)."""
+        _lib.check(L.fs_nf_mh_step(dims, _lib.ptr(packed), self.phys.c, self.C, self.proposal_seed,
+                                   self.step_count, self.chain_offset, _lib.ptr(self.E_old),
+                                   _lib.ptr(self.W_old), _lib.ptr(self.nll_old), _lib.ptr(self.pcg),
+                                   _lib.ptr(self.state), _lib.ptr(self.state_is_f32), _lib.ptr(self.accept),
+                                   _lib.ptr(self.attempts), _lib.ptr(self.accepted), _lib.ptr(self.n_accept),
+                                   _lib.ptr(self.err), flags, _lib.ptr(self._workspace()), st), "fs_nf_mh_step")
 
     # proposal rows per launch that fill the chip: 2 resident 64-chain workgroups on each
     # of the 256 CUs (a batch that already fills it keeps one step per launch)
@@ -344,15 +347,19 @@ class BatchedMonteCarlo:
             sew = torch.empty((self.C, S, 2), dtype=torch.float64, device=self.device)
         if log_accepts:
             log = torch.empty((self.C, n), dtype=torch.uint8, device=self.device)
-        _lib.check(L.fs_local_moves(self.phys.c, self.C, self.N, _lib.ptr(self.state), _lib.ptr(self.state_is_f32),
-                                    _lib.ptr(self.E_old), _lib.ptr(self.W_old), _lib.ptr(self.pcg),
-                                    _lib.ptr(self.pcg_buf), _lib.ptr(self.max_disp), _lib.ptr(self.attempts),
-                                    _lib.ptr(self.accepted), _lib.ptr(self.prev_counts), n, step0, int(adjust_every),
-                                    self.target_acceptance, int(sample_every), _lib.ptr(sxy), _lib.ptr(sew),
-                                    _lib.ptr(log), None, _lib.stream_ptr()), "fs_local_moves")
+        self._launch_local_moves(L, n, step0, int(adjust_every), int(sample_every), sxy, sew, log)
         if n > 0:
             self._moved = True
         return sxy, sew, log
+
+    def _launch_local_moves(self, L, n, step0, adjust_every, sample_every, sxy, sew, log):
+        """The launch of local_moves() (a temperature-ladder engine launches its own)."""
+        _lib.check(L.fs_local_moves(self.phys.c, self.C, self.N, _lib.ptr(self.state), _lib.ptr(self.state_is_f32),
+                                    _lib.ptr(self.E_old), _lib.ptr(self.W_old), _lib.ptr(self.pcg),
+                                    _lib.ptr(self.pcg_buf), _lib.ptr(self.max_disp), _lib.ptr(self.attempts),
+                                    _lib.ptr(self.accepted), _lib.ptr(self.prev_counts), n, step0, adjust_every,
+                                    self.target_acceptance, sample_every, _lib.ptr(sxy), _lib.ptr(sew),
+                                    _lib.ptr(log), None, _lib.stream_ptr()), "fs_local_moves")
 
     def invalidate_nll(self):
         """The cached old NLL is stale (the flow's weights changed): the next big move
@@ -511,13 +518,7 @@ class BatchedMonteCarlo:
                 if not torch.is_tensor(t) or t.dtype != dt or t.shape != (self.C,) or t.device != self.device:
                     raise ValueError(f"terms must be proposal_terms() rows for {self.C} chains on {self.device}")
             E_new, W_new, lq = E_new.contiguous(), W_new.contiguous(), lq.contiguous()
-        L = _lib.load()
-        _lib.check(L.fs_mh_accept(self.phys.c, self.C, self.N, _lib.ptr(self.E_old), _lib.ptr(self.W_old),
-                                  _lib.ptr(self.nll_old), _lib.ptr(E_new), _lib.ptr(W_new), _lib.ptr(lq),
-                                  _lib.ptr(self.pcg), _lib.ptr(self.state), _lib.ptr(self.state_is_f32),
-                                  _lib.ptr(cfg), _lib.ptr(self.accept), _lib.ptr(self.attempts),
-                                  _lib.ptr(self.accepted), _lib.ptr(self.n_accept), self.flags,
-                                  _lib.stream_ptr()), "fs_mh_accept")
+        self._launch_mh_accept(_lib.load(), E_new, W_new, lq, cfg)
         if cfg64 is not None:  # the kernel stored the float32 copy: accepted chains take the float64 config
             acc = (self.accept != 0)
             self.state.copy_(torch.where(acc[:, None, None], cfg64, self.state))
@@ -528,6 +529,15 @@ class BatchedMonteCarlo:
             self.W_old = torch.where(rej, W_cur, self.W_old)
             self._moved = False
         return self.accept
+
+    def _launch_mh_accept(self, L, E_new, W_new, lq, cfg):
+        """The accept launch of nf_big_move() (a temperature-ladder engine launches its own)."""
+        _lib.check(L.fs_mh_accept(self.phys.c, self.C, self.N, _lib.ptr(self.E_old), _lib.ptr(self.W_old),
+                                  _lib.ptr(self.nll_old), _lib.ptr(E_new), _lib.ptr(W_new), _lib.ptr(lq),
+                                  _lib.ptr(self.pcg), _lib.ptr(self.state), _lib.ptr(self.state_is_f32),
+                                  _lib.ptr(cfg), _lib.ptr(self.accept), _lib.ptr(self.attempts),
+                                  _lib.ptr(self.accepted), _lib.ptr(self.n_accept), self.flags,
+                                  _lib.stream_ptr()), "fs_mh_accept")
 
     # ------------------------------------------------------------------
     def particles(self):

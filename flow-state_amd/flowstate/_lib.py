@@ -108,6 +108,10 @@ _SIGS = {
     "fs_particle_energy": (ctypes.c_int, [_PH, _P, ctypes.c_int, _I64, ctypes.c_int32, _P, _P, _P, _P]),
     "fs_metropolis_judge": (ctypes.c_int, [ctypes.c_double, _I64, _I64] + [_P] * 5 + [_P]),
     "fs_mh_accept": (ctypes.c_int, [_PH, _I64, ctypes.c_int32] + [_P] * 14 + [ctypes.c_int, _P]),
+    "fs_mh_accept_beta": (ctypes.c_int, [_P, _PH, _I64, ctypes.c_int32] + [_P] * 14 + [ctypes.c_int, _P]),
+    "fs_nf_mh_step_beta": (ctypes.c_int, [_P, _D, _P, _PH, _I64, ctypes.c_uint64, ctypes.c_uint64, _I64] + [_P] * 11
+                           + [ctypes.c_int, _P, _P]),
+    "fs_replica_exchange": (ctypes.c_int, [_I64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32] + [_P] * 12 + [_P]),
     "fs_nf_mh_step_ws_bytes": (_I64, [_D, _I64]),
     "fs_nf_mh_step": (ctypes.c_int, [_D, _P, _PH, _I64, ctypes.c_uint64, ctypes.c_uint64, _I64] + [_P] * 11
                       + [ctypes.c_int, _P, _P]),
@@ -121,6 +125,8 @@ _SIGS = {
                        + [_I64, _I64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32] + [_P] * 5),
     "fs_local_moves_if": (ctypes.c_int, [_P, _PH, _I64, ctypes.c_int32] + [_P] * 10
                           + [_I64, _I64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32] + [_P] * 5),
+    "fs_local_moves_beta": (ctypes.c_int, [_P, _PH, _I64, ctypes.c_int32] + [_P] * 10
+                            + [_I64, _I64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32] + [_P] * 6),
     "fs_chains_copy_if": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.POINTER(LocalChains),
                                          ctypes.POINTER(LocalChains), _P]),
     "fs_local_samples_per_chain": (_I64, [_I64, _I64, ctypes.c_int32]),

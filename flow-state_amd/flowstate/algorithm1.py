@@ -582,7 +582,12 @@ def testing_phase(bmc: BatchedMonteCarlo, test_configs, attempts, interval, samp
     stream, the big moves on the main stream), "local" (_Speculator: each big move beside
     the next attempt's local moves) or False (one phase after the other).  The engine's
     chain buffers (bmc.state, bmc.pcg, ...) may afterwards be other tensors of the same
-    shape: read them from bmc after the call, not through references taken before it."""
+    shape: read them from bmc after the call, not through references taken before it.
+    Not for a temperature ladder (MCMC.TemperedMonteCarlo): the pipeline and its speculation
+    assume one beta for all chains, so such an engine raises NotImplementedError."""
+    if getattr(bmc, "is_ladder", False):
+        raise NotImplementedError("testing_phase runs chains at one beta; a temperature ladder "
+                                  "(TemperedMonteCarlo) has its own loop, sweeps()")
     C = bmc.C
     cfg = torch.as_tensor(test_configs)
     if cfg.dtype != torch.float32:

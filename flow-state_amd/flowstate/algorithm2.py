@@ -87,7 +87,12 @@ class Algorithm2:
         also computes the importance weights of its samples against the engine's target
         (analysis.sample_analysis(reweight=bmc.phys)) and writes
         importance_cycle_{c}_data.json (io.write_importance); the chains and every other
-        file are those of a run without it."""
+        file are those of a run without it.
+        Not for a temperature ladder (MCMC.TemperedMonteCarlo): the training data and the
+        target are one temperature's, so such an engine raises NotImplementedError."""
+        if getattr(bmc, "is_ladder", False):
+            raise NotImplementedError("Algorithm2 trains on chains at one beta; a temperature ladder "
+                                      "(TemperedMonteCarlo) is not supported")
         self.bmc, self.model = bmc, model
         self.batch_size, self.lr, self.wd, self.alpha = int(batch_size), float(lr), float(weight_decay), float(alpha)
         self.sf = int(sampling_frequency)

@@ -151,6 +151,16 @@ def write_chain_diagnostics(directory, result):
     return path
 
 
+def write_tempering(directory, summary):
+    """tempering_data.json: TemperedMonteCarlo.swap_summary() (plain floats, ints and lists:
+    per rung pair the exchange attempts, accepts and rate; the round trips per ladder and in
+    total; per temperature the mean energy, the move acceptance and the well populations)."""
+    path = os.path.join(directory, "tempering_data.json")
+    with open(path, "w") as f:
+        json.dump(summary, f)
+    return path
+
+
 def save_model_checkpoint(directory, cycle, model):
     """model_checkpoint_cycle_{cycle}.pth (main_algorithm_2.py:469-470)."""
     import torch

@@ -242,6 +242,50 @@ int fs_nf_mh_step(const fs_flow_dims *d, const void *packed, const fs_phys *p, i
                   int64_t *attempts, int64_t *accepted, unsigned long long *n_accept,
                   int32_t *err, int flags, void *ws, void *stream);
 
+/* Temperature ladders (not in the reference): fs_mh_accept and fs_nf_mh_step with a
+ * per-chain inverse temperature.  beta_c [C] float64 (device) replaces p->beta in the accept
+ * ratio of chain c and in nothing else: the proposals, their log q and the energies do not
+ * depend on beta, so chain c runs bit for bit as in the plain call at p->beta = beta_c[c],
+ * with every flag (FS_MH_HYBRID and FS_MH_SINGLE_PASS go through the same accept).
+ * beta_c = NULL: p->beta for every chain, the plain call.  The other arguments, their
+ * checks and the workspace are those of the plain call.  The multi-step and banked forms
+ * have no ladder variant. */
+int fs_mh_accept_beta(const double *beta_c, const fs_phys *p, int64_t C, int32_t N, double *E_old, double *W_old,
+                      double *nll_old, const double *E_new, const double *W_new, const float *log_q_new,
+                      uint64_t *pcg, double *state, uint8_t *state_is_f32, const float *config, uint8_t *accept,
+                      int64_t *attempts, int64_t *accepted, unsigned long long *n_accept, int flags, void *stream);
+int fs_nf_mh_step_beta(const double *beta_c, const fs_flow_dims *d, const void *packed, const fs_phys *p, int64_t C,
+                       uint64_t seed, uint64_t step, int64_t chain_offset, double *E_old, double *W_old,
+                       double *nll_old, uint64_t *pcg, double *state, uint8_t *state_is_f32, uint8_t *accept,
+                       int64_t *attempts, int64_t *accepted, unsigned long long *n_accept, int32_t *err, int flags,
+                       void *ws, void *stream);
+
+/* One replica-exchange (parallel tempering) round over R ladders of T rungs, C = R T
+ * chains: chain r T + t is rung t of ladder r, beta_c [C] its inverse temperature
+ * (temperatures ascending in t).  Round `parity` (0 or 1) pairs rungs (t, t + 1) for
+ * t = parity, parity + 2, ... < T - 1; with i = r T + t, j = i + 1, in double:
+ *   E_i or E_j not finite: reject, no draw;
+ *   d = (beta_i - beta_j) (E_i - E_j);  d >= 0: accept, no draw;
+ *   else accept iff Generator.random() < exp(d), one draw of chain i's PCG64 stream pcg[i]
+ *   (pcg [C][4] as fs_pcg64_seed; the 32-bit half buffer of fs_local_moves is not touched).
+ * A chain index is a temperature, so an accepted pair exchanges its configurations:
+ * state [C][N][2] float64 (16-byte aligned), state_is_f32, E, W, nll [C] and replica_id
+ * [C] int32 (the label of the configuration at each chain; the caller starts it as t).  The
+ * PCG64 states and everything else per chain stay.  swap_attempts / swap_accepts [C] int64,
+ * indexed by the pair's lower chain i, count every pair / the accepted ones.  trip_dir [C]
+ * int8 and round_trips [C] int64 follow the labels (index r T + label; the caller starts
+ * label 0 with trip_dir 1, the others with 0): after its exchange, a pair holding rung 0
+ * counts a round trip for the label now there if its trip_dir is 2 and sets it to 1; a pair
+ * holding rung T - 1 turns a trip_dir of 1 of the label now there into 2.
+ * W, nll, state_is_f32 and the four bookkeeping arrays are nullable (round_trips needs
+ * trip_dir, trip_dir needs replica_id).  One launch, one wave per pair; no atomics, no
+ * allocation, capture-safe.  FS_EINVAL, naming the argument: T < 2, parity outside {0, 1},
+ * N outside 1..64, a NULL beta_c, state, E or pcg. */
+int fs_replica_exchange(int64_t R, int32_t T, int32_t N, int32_t parity, const double *beta_c, double *state,
+                        uint8_t *state_is_f32, double *E, double *W, double *nll, uint64_t *pcg,
+                        int32_t *replica_id, int64_t *swap_attempts, int64_t *swap_accepts, int8_t *trip_dir,
+                        int64_t *round_trips, void *stream);
+
 /* S consecutive fs_nf_mh_step calls (steps step0 .. step0+S-1) with the same results:
  * the proposals, their log q and energies do not depend on the chain states, so each
  * pass runs once over S*C rows (a small C then fills the chip), followed by the S
@@ -701,6 +745,19 @@ int fs_local_moves_if(const uint8_t *gate, const fs_phys *p, int64_t C, int32_t 
                       int64_t n_moves, int64_t step0, int32_t adjust_every, double target_acceptance,
                       int32_t sample_every, double *samples_xy, double *samples_ew, uint8_t *accept_log,
                       unsigned long long *n_accept, void *stream);
+
+/* fs_local_moves with a per-chain inverse temperature (a temperature ladder, not in the
+ * reference): beta_c [C] float64 (device) replaces p->beta in chain c's accept and in
+ * nothing else (the draws, their order, the inf / NaN rules and the counters are
+ * fs_local_moves's), so chain c runs bit for bit as in a plain launch at p->beta =
+ * beta_c[c]; NULL: p->beta for every chain.  gate (nullable): fs_local_moves_if's device
+ * byte. */
+int fs_local_moves_beta(const double *beta_c, const fs_phys *p, int64_t C, int32_t N, double *state,
+                        const uint8_t *state_is_f32, double *E, double *W, uint64_t *pcg, uint64_t *pcg_buf,
+                        double *max_disp, int64_t *attempts, int64_t *accepted, int64_t *prev_counts,
+                        int64_t n_moves, int64_t step0, int32_t adjust_every, double target_acceptance,
+                        int32_t sample_every, double *samples_xy, double *samples_ew, uint8_t *accept_log,
+                        unsigned long long *n_accept, const uint8_t *gate, void *stream);
 
 /* The per-chain arrays fs_local_moves reads and writes (state [C][N][2], the rest [C],
  * pcg [C][4], pcg_buf / prev_counts [C][2]); state_is_f32, W and prev_counts nullable
